@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- the driver contract.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no torchrun environment re-launches itself under torch.distributed.run (one rank per GPU, RCCL);
@@ -10,12 +10,19 @@ it refuses to run if the box has fewer than N GPUs -- it never reports fewer ran
 Headline metric (BASELINE.json): GS views/s at 1 M Gaussians, 640x480 (configs[1]) -- a "step" is one pass of the
 rasterizer forward over one batch of `--views` cameras of the same synthetic 1 M-Gaussian scene (inputs resident in HBM
 before the timed region; cameras are 200-byte host structs), through the DEFAULT path of the wrapper: every call ordered on
-the caller's stream, like upstream's.  The opt-in `static_scene=True` mode (two calls in flight on internal streams,
-gaussreg_amd/rasterizer.py _FramePipe) is timed separately and reported as `config.static_scene_views_per_s`.
+the caller's stream, like upstream's.  Exactly `--steps` steps are timed, after `--warmup` untimed ones, with the per-kernel
+event timers off; `ms_per_step` is the time of one of them.
+
+A plain run does only that: set up, warm up, time the steps, write the outputs of the last step if `--dump-outputs DIR` is
+given (dump_outputs below), print the line.  Everything else below runs with `--full` only.
+
+`--full`: the opt-in `static_scene=True` mode (two calls in flight on internal streams, gaussreg_amd/rasterizer.py
+_FramePipe) is timed separately and reported as `config.static_scene_views_per_s`; the per-kernel figures of the headline
+(`roofline`) come from a second, instrumented pass of the same steps.
 The driver's record keeps the scalars of `config`, `roofline` and `cpu_baseline` and the tail of the line: the second half of
 the metric (radius_neighbors Mpts/s and its roofline fractions) and the one-camera figures are therefore ALSO scalars there
 (`roofline.radius_*`, `config.single_view_*`), and the line ends with a short `summary`.
-The same JSON line also carries, each timed the same way
+With `--full` the same JSON line also carries, each timed the same way
 (own warmup, barrier + synchronize on both sides, MAX over ranks):
     "single_view"       views/s through diff_gaussian_rasterization.GaussianRasterizer.forward, ONE camera per call
                         (the drop-in boundary number)
@@ -78,6 +85,12 @@ def parse(argv=None):
                          "one JSON line and exit -- no kernels, seconds per rank (tools/first_8gpu_run.md)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="process-group backend; gloo exists for the CPU suite's test of --dry (same code path, CPU tensors)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other section as well (static-scene pass, per-kernel roofline, ballot "
+                         "ranking, one-camera loops, fast_exp, radius_neighbors, pairs, extras, CPU baselines); the --no-* "
+                         "options switch single sections off.  Off by default: a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0) as DIR/<name>.npy")
     return ap.parse_args(argv)
 
 
@@ -371,6 +384,32 @@ def per_step_ms(L, names, steps):
     return out
 
 
+DUMP_SAMPLE = 4_000_000   # elements kept of an array larger than this (16 MB of float32; two such arrays in a dump)
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """`--dump-outputs DIR`: write {name: tensor or array} as DIR/<name>.npy, integers and float32 as float32, int64 and float64
+    as float64 (exact for the values the rasterizer returns).  An array of more than DUMP_SAMPLE elements is written as the
+    DUMP_SAMPLE elements at sorted flat positions np.random.default_rng(seed).choice(numel, DUMP_SAMPLE, replace=False), the
+    same positions for the same shape, so two builds compare element for element.  Returns {name: (shape, numel written)}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, a in arrays.items():
+        t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        flat = t.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            pos = np.sort(np.random.default_rng(seed).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            flat = flat.index_select(0, torch.from_numpy(pos).to(flat.device))
+            name = name + "_sample"
+        wide = flat.dtype in (torch.float64, torch.int64)
+        host = flat.cpu().numpy().astype(np.float64 if wide else np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), host if flat.numel() != t.numel() else host.reshape(tuple(t.shape)))
+        written[name] = (tuple(t.shape), int(host.size))
+    return written
+
+
 def run_gpu(h, args):
     import numpy as np
     import torch
@@ -399,9 +438,25 @@ def run_gpu(h, args):
         last["radii"] = radii
 
     raster_step()  # allocate / page in before anything is timed
+    L.gr_timing_enable(0)
     L.gr_timing_reset()
+    elapsed = h.timed(raster_step, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"color": last["img"], "radii": last["radii"], "num_rendered": last["nr"]})
+    metric = "GS views/sec @1M pts 640x480 (+ radius_neighbors Mpts/sec, see radius_neighbors)"
+    if not args.full:
+        R_total = float(sum(last["nr"]))
+        return order_line(throughput_line(
+            h, metric, "views/s", V, args.steps, args.warmup, elapsed,
+            {"dtype": "f32", "data": "synthetic", "full": False,
+             "config": {"workload": f"diff_gaussian_rasterization forward: {P} synthetic Gaussians (SH deg 3), {W}x{H}, "
+                                    f"{V} views per step per GPU (configs[1])",
+                        "gaussians": P, "width": W, "height": H, "views_per_step": V,
+                        "instances_per_view": round(R_total / V, 1), "parallelism": f"per-view sharding x{world}"}}))
+
+    # --full: the per-kernel figures of the same steps, from a second pass with the event timers on
     L.gr_timing_enable(1)
-    elapsed = h.timed(raster_step, args.steps, args.warmup, after_warmup=L.gr_timing_reset)
+    h.timed(raster_step, args.steps, 1, after_warmup=L.gr_timing_reset)
     blend_ms, blend_n = timing_read(L, "raster_blend")
     raster_kernels = per_step_ms(L, ["raster_preprocess", "raster_depth_sort", "raster_bin", "raster_sort", "raster_blend"],
                                  args.steps)
@@ -426,9 +481,9 @@ def run_gpu(h, args):
     # plus the image write 12*H*W per view
     blend_bytes = R_total * (4 + 8 + 16 + 12) + 12.0 * H * W * V
     line = throughput_line(
-        h, "GS views/sec @1M pts 640x480 (+ radius_neighbors Mpts/sec, see radius_neighbors)", "views/s", V, args.steps,
+        h, metric, "views/s", V, args.steps,
         args.warmup, elapsed,
-        {"dtype": "f32", "data": "synthetic",
+        {"dtype": "f32", "data": "synthetic", "full": True,
          "config": {"workload": f"diff_gaussian_rasterization forward: {P} synthetic Gaussians (SH deg 3), {W}x{H}, "
                                 f"{V} views per step per GPU (configs[1])",
                     "gaussians": P, "width": W, "height": H, "views_per_step": V,
@@ -838,7 +893,7 @@ def order_line(line):
     """Key order of the printed line: the contract's fields first, the long sections in the middle, and a short `summary` of
     the figures that answer the metric LAST (the driver keeps the line's tail and the scalars of config / roofline / cpu_baseline)."""
     head = ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
-            "dtype", "data", "config", "roofline", "cpu_baseline"]
+            "dtype", "data", "full", "config", "roofline", "cpu_baseline"]
     out = {k: line[k] for k in head if k in line}
     for k in ("extras", "pairs", "fast_exp", "single_view", "radius_neighbors"):
         if k in line:

@@ -17,6 +17,15 @@ def c1_points():
     return torch.rand(20000, 3, generator=g).numpy()
 
 
+def ext_random_case(seed):
+    """Seeded two-batch radius / grid inputs (tests/test_oracle_ext.py, tests/golden/gen_golden_ext_random.py)."""
+    rng = np.random.default_rng(seed)
+    s = (rng.random((5000, 3)) * [2.0, 1.0, 0.5]).astype(np.float32)
+    q = (rng.random((3000, 3)) * [2.2, 1.0, 0.5] - 0.1).astype(np.float32)
+    return {"q": q, "s": s, "q_lengths": np.array([1000, 2000], np.int64), "s_lengths": np.array([3000, 2000], np.int64),
+            "radius": 0.09, "voxel": 0.04}
+
+
 def sqdist_f32(q, s):
     """The reference metric (nanoflann.hpp:432-440) in numpy fp32: ((dx*dx + dy*dy) + dz*dz)."""
     d = q.astype(np.float32) - s.astype(np.float32)

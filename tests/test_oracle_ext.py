@@ -1,11 +1,11 @@
 """CPU: pin oracle/{radius_neighbors_oracle.c, grid_subsample_oracle.cpp} against golden vectors
-that were produced by the reference's own C++ (tests/golden/gen_golden_ext.py), and -- where
-oracle/_ref is present -- against the reference core directly on fresh random inputs."""
+that were produced by the reference's own C++ (tests/golden/gen_golden_ext.py, gen_golden_ext_random.py); where
+oracle/_ref is present, the reference core also recomputes the seeded random cases."""
 import numpy as np
 import pytest
 
 from oracle import capi
-from helpers import load_golden, c1_points, assert_neighbors_equal_up_to_ties
+from helpers import load_golden, c1_points, assert_neighbors_equal_up_to_ties, ext_random_case
 
 
 def test_c1_inputs_reproducible():
@@ -83,17 +83,21 @@ def test_pyramid_matches_reference():
         r *= 2
 
 
-@pytest.mark.skipif(not capi.have_ref(), reason="oracle/_ref not built (reference not mounted)")
 @pytest.mark.parametrize("seed", [3, 4])
 def test_restatement_vs_ref_random(seed):
-    rng = np.random.default_rng(seed)
-    s = (rng.random((5000, 3)) * [2.0, 1.0, 0.5]).astype(np.float32)
-    q = (rng.random((3000, 3)) * [2.2, 1.0, 0.5] - 0.1).astype(np.float32)
-    sl = np.array([3000, 2000], np.int64)
-    ql = np.array([1000, 2000], np.int64)
-    want = capi.ref_radius_neighbors(q, s, ql, sl, 0.09)
-    got = capi.radius_neighbors(q, s, ql, sl, 0.09)
+    """Against the reference core's outputs on these inputs: stored in ext_random.npz (gen_golden_ext_random.py), and
+    recomputed by the core itself where oracle/_ref is built (which also pins the fixture)."""
+    c = ext_random_case(seed)
+    q, s, ql, sl = c["q"], c["s"], c["q_lengths"], c["s_lengths"]
+    g = load_golden("ext_random.npz")
+    assert np.array_equal(q, g[f"q_{seed}"]) and np.array_equal(s, g[f"s_{seed}"])
+    want = g[f"neighbors_{seed}"].astype(np.int64)
+    sp_w, sl_w = g[f"s_points_{seed}"], g[f"sub_lengths_{seed}"]
+    if capi.have_ref():
+        assert np.array_equal(capi.ref_radius_neighbors(q, s, ql, sl, c["radius"]), want)
+        sp_r, sl_r = capi.ref_grid_subsampling(s, sl, c["voxel"])
+        assert np.array_equal(sl_r, sl_w) and np.array_equal(sp_r.view(np.uint32), sp_w.view(np.uint32))
+    got = capi.radius_neighbors(q, s, ql, sl, c["radius"])
     assert_neighbors_equal_up_to_ties(got, want, q, s, ql, sl)
-    sp_w, sl_w = capi.ref_grid_subsampling(s, sl, 0.04)
-    sp_g, sl_g = capi.grid_subsampling(s, sl, 0.04)
+    sp_g, sl_g = capi.grid_subsampling(s, sl, c["voxel"])
     assert np.array_equal(sl_w, sl_g) and np.array_equal(sp_w.view(np.uint32), sp_g.view(np.uint32))

@@ -9,7 +9,7 @@
 # The counter passes use the same command as the first CSV.
 R=${1:-r03}
 cd $GRAFT_REPO_ROOT
-B="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --pairs 0 --no-single-view --no-static-scene"
+B="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --pairs 0 --no-single-view --no-static-scene"
 bash tools/prof.sh bench $GRAFT_REPO_ROOT/$B > /dev/null 2>&1
 bash tools/prof.sh sv $GRAFT_REPO_ROOT/tools/single_view_loop.py > /dev/null 2>&1
 bash tools/prof.sh extras $GRAFT_REPO_ROOT/tools/bench_extras.py > /dev/null 2>&1

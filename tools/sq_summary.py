@@ -41,7 +41,7 @@ def main():
                     row[c.lower() + "_frac_of_wave_cycles"] = round(per[c] / per["SQ_WAVE_CYCLES"], 3)
         row["profiled_duration_us_avg"] = round(sum(dur[k]) / len(dur[k]), 1)
         kernels.append(row)
-    doc = {"note": "rocprofv3 --pmc (SQ counters, two passes of 8, tools/pmc.sh) over python bench.py --steps 3 --warmup 1 "
+    doc = {"note": "rocprofv3 --pmc (SQ counters, two passes of 8, tools/pmc.sh) over python bench.py --full --steps 3 --warmup 1 "
                    "--no-cpu-baseline.  SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_* count quad-cycles (MI355X_MICROARCH.md). "
                    "valu_issue_us = SQ_INSTS_VALU x 4 cycles / 1024 SIMDs / 2.4 GHz: the time the VALU pipes alone need; compare "
                    "with the kernel's duration (profiled_duration_us_avg, or profiles/*_bench_kernel_stats.csv).",
