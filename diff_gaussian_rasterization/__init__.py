@@ -1,4 +1,4 @@
-"""``diff_gaussian_rasterization`` drop-in (forward only), backed by the gfx950 rasterizer."""
+"""``diff_gaussian_rasterization`` drop-in (differentiable: forward and backward), backed by the gfx950 rasterizer."""
 from gaussreg_amd.rasterizer import (  # noqa: F401
     GaussianRasterizationSettings,
     GaussianRasterizer,

@@ -65,6 +65,11 @@ SIGNATURES.update({
     "gr_raster_lds_atomics_lane_ordered": (c_int, []),
     "gr_raster_ballot_ranking": (c_int, [c_int]),
     "gr_raster_mark_visible": (c_int, [c_i64, c_void, ctypes.POINTER(c_f32), c_void, c_void]),
+    "gr_raster_render_keep": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
+                                      c_void, c_int, c_void]),
+    "gr_raster_backward_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
+    "gr_raster_backward": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size, c_void,
+                                   c_size, c_i64p, c_void, c_void, c_void, c_int] + [c_void] * 8 + [c_void, c_size, c_void]),
 })
 
 

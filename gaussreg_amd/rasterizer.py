@@ -10,8 +10,12 @@ upstream one (graphdeco-inria/diff-gaussian-rasterization, diff_gaussian_rasteri
     GaussianRasterizer.markVisible(positions) -> BoolTensor
 
 plus `rasterize_views(...)`: many cameras over one Gaussian set in one launch sequence (the
-throughput path: per-Gaussian inputs are read once per batch).  Forward only: outputs carry no
-autograd graph (fine registration in GaussReg only renders).
+throughput path: per-Gaussian inputs are read once per batch).
+
+Differentiable like upstream: when grad mode is on and an input requires grad, the call goes through an autograd
+Function (_RasterizeViews) whose backward is the HIP backward of include/gaussreg_hip.h (gr_raster_backward): gradients
+for means3D, means2D (dL/dNDC), shs / colors_precomp, opacities, scales / rotations / cov3D_precomp; radii is not
+differentiable, cameras get none.  Otherwise every call takes the forward-only path, unchanged.
 """
 import ctypes
 import os
@@ -193,9 +197,96 @@ def reset_frame_pipe():
             p.stamp = p.keep = p.ready = p.ptrs = None
 
 
+def _dev_f32_grad(t, dev):
+    """_dev_f32 for the autograd path: a differentiable conversion (no detach), so gradients reach the caller's tensor in
+    its own dtype and device."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("rasterizer inputs must be tensors")
+    return t.to(device=dev, dtype=torch.float32).contiguous()
+
+
+class _RasterizeViews(torch.autograd.Function):
+    """Autograd forward (gr_raster_preprocess + gr_raster_render_keep, serial, on the caller's stream) and HIP backward
+    (gr_raster_backward).  Inputs arrive as fp32, contiguous, on the device (converted differentiably by the caller)."""
+
+    @staticmethod
+    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov):
+        dev = m.device
+        L = _lib.lib()
+        V, views, H, W = vb.count, vb.array, vb.height, vb.width
+        P = m.shape[0]
+        M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
+        st = _lib.stream_ptr(dev)
+        nr = (ctypes.c_int64 * (V + 1))()
+        hw = H * W
+        state = torch.empty(5 * V * hw, dtype=torch.float32, device=dev)  # colour, final_T, n_contrib (gr_raster_render_keep)
+        radii = torch.empty((V, P), dtype=torch.int32, device=dev)
+        gbytes = L.gr_raster_geom_bytes(P, V, W, H) + 256
+        geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+        ptrs = (_lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov))
+        _lib.check(L.gr_raster_preprocess(P, M, *ptrs, views, V, _lib.ptr(radii), _lib.ptr(geom), gbytes, nr, st))
+        total = sum(int(nr[v]) for v in range(V))
+        binb = torch.empty(L.gr_raster_bin_bytes(total, W, H, V) + 256, dtype=torch.uint8, device=dev)
+        _lib.check(L.gr_raster_render_keep(P, views, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel(),
+                                           _lib.ptr(state), flags, st))
+        ctx.vb, ctx.flags, ctx.one, ctx.M, ctx.nr = vb, flags, one, M, nr
+        ctx.geom, ctx.binb, ctx.state = geom, binb, state[3 * V * hw:]  # final_T, n_contrib
+        ctx.m2d = None if m2d is None else (m2d.shape, m2d.dtype, m2d.device)
+        ctx.save_for_backward(m, op, sh, cp, sc, rot, cov)
+        # a tensor of its own (not a view of the state allocation): callers may modify the image in place, as upstream's
+        color = state[:3 * V * hw].view((3, H, W) if one else (V, 3, H, W)).clone()
+        radii = radii.view(P) if one else radii
+        ctx.mark_non_differentiable(radii)
+        box.extend(int(nr[v]) for v in range(V))  # num_rendered (not an autograd output)
+        return color, radii
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_color, grad_radii):
+        m, op, sh, cp, sc, rot, cov = ctx.saved_tensors
+        dev = m.device
+        L = _lib.lib()
+        vb = ctx.vb
+        V, H, W = vb.count, vb.height, vb.width
+        P = m.shape[0]
+        need = ctx.needs_input_grad
+        if grad_color is None:
+            grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
+        g = grad_color.to(device=dev, dtype=torch.float32).contiguous()
+
+        def out(t, i):
+            return torch.empty_like(t) if (t is not None and need[i]) else None
+        dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
+                                             out(cov, 11))
+        dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
+        hw = H * W
+        final_T = ctx.state[:V * hw]
+        n_contrib = ctx.state[V * hw:]
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            sbytes = L.gr_raster_backward_bytes(P, V, W, H, ctx.nr) + 256
+            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.gr_raster_backward(
+                P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov),
+                vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(), ctx.nr,
+                _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), ctx.flags, _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh),
+                _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov), _lib.ptr(scratch),
+                scratch.numel(), st))
+        if dm2 is not None:
+            shape, dtype, device = ctx.m2d
+            dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
+        return None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov
+
+
+def _wants_grad(*ts):
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
 def rasterize_views(settings, means3D, opacities, shs=None,
                     colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, fast_exp=None, _one=False,
-                    static_scene=False):
+                    static_scene=False, *, means2D=None):
     """Render the same Gaussians from len(settings) cameras (`settings`: a sequence of
     GaussianRasterizationSettings, or a prebuilt ViewBatch).
 
@@ -207,7 +298,12 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     oracle -- the image is within 1e-5 relative of the bit-exact one (default False: bit-exact).
     `static_scene=True` (extension): consecutive calls over the same, unmodified scene tensors overlap on two internal
     streams (_FramePipe: read its contract first -- only writes that bump the tensors' version counters are seen).
-    (`_one`: internal, one camera -- the outputs come back as (3,H,W) and (P,), no view ops on the way out.)"""
+    (`_one`: internal, one camera -- the outputs come back as (3,H,W) and (P,), no view ops on the way out.)
+
+    Autograd: when grad mode is on and any input requires grad, the call is differentiable (see the module docstring);
+    it then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
+    `means2D` (keyword only, extension): a (V, P, 3) tensor (upstream's (P, 3) screen-space means for one camera) whose
+    .grad receives dL/d(NDC position) per view; its values are not read."""
     dev = means3D.device if means3D.is_cuda else _lib.require_gpu()
     L = _lib.lib()
     n_pts = int(means3D.shape[0])
@@ -222,6 +318,30 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     if has_sr == has_cov or (given(scales) != given(rotations)):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
     vb = settings if isinstance(settings, ViewBatch) else ViewBatch(settings)
+    if _wants_grad(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp):
+        if means3D.dim() != 2 or means3D.shape[1] != 3:
+            raise RuntimeError("means3D must have dimensions (num_points, 3)")
+        if means2D is not None:
+            ok = (tuple(means2D.shape) == (vb.count, n_pts, 3) or
+                  (vb.count == 1 and tuple(means2D.shape) == (n_pts, 3)))
+            if not ok:
+                raise ValueError(f"means2D must have shape ({vb.count}, {n_pts}, 3)" +
+                                 (f" or ({n_pts}, 3)" if vb.count == 1 else "") + f", got {tuple(means2D.shape)}")
+        home = torch.cuda.current_device()
+        if home != dev.index:
+            torch.cuda.set_device(dev)
+        box = []
+        try:
+            color, radii = _RasterizeViews.apply(
+                vb, _flags(fast_exp), _one and vb.count == 1, box, _dev_f32_grad(means3D, dev), means2D,
+                _dev_f32_grad(opacities, dev), _dev_f32_grad(shs, dev) if given(shs) else None,
+                _dev_f32_grad(colors_precomp, dev) if given(colors_precomp) else None,
+                _dev_f32_grad(scales, dev) if has_sr else None, _dev_f32_grad(rotations, dev) if has_sr else None,
+                _dev_f32_grad(cov3D_precomp, dev) if has_cov else None)
+        finally:
+            if home != dev.index:
+                torch.cuda.set_device(home)
+        return color, radii, box
     V, views, H, W = vb.count, vb.array, vb.height, vb.width
     m = _dev_f32(means3D, dev, "means3D")
     if m.dim() != 2 or m.shape[1] != 3:
@@ -326,7 +446,8 @@ def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales,
     """`raster_settings`: GaussianRasterizationSettings, or a one-camera ViewBatch built from it (marshalled once)."""
     vb = raster_settings if isinstance(raster_settings, ViewBatch) else [raster_settings]
     color, radii, _ = rasterize_views(vb, means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp,
-                                      fast_exp=fast_exp, _one=True, static_scene=static_scene)
+                                      fast_exp=fast_exp, _one=True, static_scene=static_scene,
+                                      means2D=means2D if isinstance(means2D, torch.Tensor) and means2D.requires_grad else None)
     return color, radii
 
 

@@ -36,7 +36,7 @@ int gr_version(void);
 
 /* Optional per-kernel timing with HIP events recorded on the launch stream (measurement aid, off
  * by default).  Timer names: "radius_bin", "radius_count", "radius_fill", "radius_fused", "raster_preprocess",
- * "raster_depth_sort", "raster_bin", "raster_blend", "fps", "sinkhorn", "lgr", "ransac", "kpconv", "group_norm",
+ * "raster_depth_sort", "raster_bin", "raster_blend", "raster_bwd_slots", "raster_bwd_render", "raster_bwd_preprocess", "fps", "sinkhorn", "lgr", "ransac", "kpconv", "group_norm",
  * "geo_embedding", "rpe_attention", "rpe_scores", "gs_fuse".  gr_timing_read waits for the recorded events and returns total ms / launches. */
 void gr_timing_enable(int on);
 void gr_timing_reset(void);
@@ -149,7 +149,7 @@ int gr_grid_subsample(const float* points, const int64_t* h_lengths, int64_t n, 
                       int64_t* h_total_m, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * 3D-Gaussian-splatting rasterizer, forward only -- the op GaussReg's fine-registration rendering
+ * 3D-Gaussian-splatting rasterizer, forward and backward -- the op GaussReg's fine-registration rendering
  * needs (BASELINE.json north_star).  NOT PRESENT in the reference tree (the only
  * trace is the acknowledgement at README.md:150); the interface replaced is the public
  *   diff_gaussian_rasterization.GaussianRasterizer.forward / .markVisible
@@ -245,6 +245,32 @@ int gr_raster_lds_atomics_lane_ordered(void);
  * starts the process with 1); any other value only queries.  Process-wide; returns the previous setting.  Same images
  * either way (tests/test_gpu_rasterizer.py); bench.py reports both (config.ballot_ranking_views_per_s). */
 int gr_raster_ballot_ranking(int on);
+/* Autograd forward: gr_raster_render_ex that also keeps the per-pixel state the backward starts from.  `out_state` is ONE
+ * allocation: out_color (num_views, 3, H, W) fp32, then final_T (num_views, H, W) fp32 (final transmittance), then n_contrib
+ * (num_views, H, W) int32 (1 + index of the last blended entry in the tile's list, 0 = none).  The image is bit-identical
+ * to gr_raster_render_ex's.  Call it after gr_raster_preprocess (no speculation); keep geom and bin for the backward. */
+int gr_raster_render_keep(int64_t P, const gr_raster_view* h_views, int num_views, const int64_t* h_num_rendered,
+                          const void* geom, size_t geom_bytes, void* bin, size_t bin_bytes, float* out_state, int flags,
+                          void* stream);
+/* Backward of gr_raster_preprocess + gr_raster_render_keep (same inputs, views, geom, bin, h_num_rendered).  Gradient
+ * contract (upstream's conventions; INTEGRATION.md "Rasterizer backward"):
+ *   - the derivative of THIS forward; dL_dmeans2D[v][g][0:2] = dL/d(NDC position) (upstream's 0.5 W, 0.5 H), [2] = 0
+ *   - alpha = min(opacity G, 0.99) is straight-through (dalpha/dG = opacity); the 1.3 tan(fov) clamp of x/z, y/z and the
+ *     SH -> RGB max(., 0) zero the gradient where active; skipped (pixel, Gaussian) pairs contribute nothing
+ *   - rotations: the raw quaternion; SH coefficients past (sh_degree + 1)^2 and culled Gaussians get zeros
+ *   - views summed in view order; no atomics: bitwise reproducible; GR_RASTER_FAST_EXP must match the forward's flags
+ * dL_dcolor: (num_views, 3, H, W).  Null output pointers are not written.  Outputs are written (not accumulated).
+ * scratch: gr_raster_backward_bytes(P, num_views, W, H, h_num_rendered) bytes.  Synchronises `stream` once, early: the
+ * per-instance slot layout is checked against sum h_num_rendered (an error if geom / bin / h_num_rendered do not come from
+ * the same forward call). */
+size_t gr_raster_backward_bytes(int64_t P, int num_views, int width, int height, const int64_t* h_num_rendered);
+int gr_raster_backward(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                       const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                       const gr_raster_view* h_views, int num_views, const void* geom, size_t geom_bytes, const void* bin,
+                       size_t bin_bytes, const int64_t* h_num_rendered, const float* final_T, const int32_t* n_contrib,
+                       const float* dL_dcolor, int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs,
+                       float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                       void* scratch, size_t scratch_bytes, void* stream);
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (markVisible). */
 int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewmatrix,
                            uint8_t* present, void* stream);
