@@ -815,8 +815,9 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int CELL = 4;
 constexpr int NCELL = (TILE / CELL) * (TILE / CELL);  // 16
 
-__device__ __forceinline__ float lds_f32(const float* plane, unsigned int byte_off) {
-  return *reinterpret_cast<const float*>(reinterpret_cast<const char*>(plane) + byte_off);
+template <typename T>
+__device__ __forceinline__ T lds_at(const T* base, unsigned int byte_off) {
+  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + byte_off);
 }
 // fmaxf without the canonicalising v_max(x, x) in front (x is the result of an fma here: never a signalling NaN)
 __device__ __forceinline__ float max_f32_raw(float a, float b) {
@@ -831,8 +832,41 @@ __device__ __forceinline__ float min_f32_raw(float a, float b) {  // fminf, same
   return r;
 }
 
+// One list entry up to alpha, in the oracle's scalar order: dx, dy, q, power, exp_det(power) (or the hardware exponential
+// under FAST_EXP, see blend_kernel), opacity * e, min(., 0.99).  a = {px, py, conic x, conic z}, cy = conic y, op = opacity.
+template <bool FAST_EXP>
+__device__ __forceinline__ float entry_alpha(float4 a, float cy, float op, f32x2 pf, float& power) {
+  // {dx, dy} and {cx dx, cz dy} are packed within the entry: their operands already sit in register pairs of the record.
+  // The rest is scalar and written as instructions, so that the compiler does not pair it across the two entries of a
+  // step (that needs eight v_mov per step to build the register pairs, more VALU cycles than it saves).
+  const f32x2 d = f32x2{a.x, a.y} - pf;
+  const f32x2 m = f32x2{a.z, a.w} * d;
+  float q, t;
+  asm("v_mul_f32 %0, %1, %2" : "=v"(q) : "v"(m.y), "v"(d.y));
+  asm("v_fma_f32 %0, %1, %2, %0" : "+v"(q) : "v"(m.x), "v"(d.x));         // q = fma(cx dx, dx, (cz dy) dy)
+  asm("v_mul_f32 %0, %1, %2" : "=v"(t) : "v"(cy), "v"(d.x));
+  asm("v_mul_f32 %0, %0, %1" : "+v"(t) : "v"(d.y));
+  asm("v_fma_f32 %0, -0.5, %1, -%2" : "=v"(power) : "v"(q), "v"(t));     // power = fma(-0.5, q, -((cy dx) dy))
+  float e;
+  if (FAST_EXP) {
+    e = __builtin_amdgcn_exp2f(power * 1.44269504088896341f);
+  } else {
+    // exp_det(): 13 issue slots (the Cephes form of rounds 1 - 5 took 20)
+    const float x = max_f32_raw(power, -86.0f);
+    const float tm = x * 1.44269504088896341f + 12582912.0f;
+    const float f = fmaf(x, 1.44269504088896341f, -(tm - 12582912.0f));
+    float pl = fmaf(1.3264815788716078e-3f, f, 9.671512059867382e-3f);
+    pl = fmaf(pl, f, 5.550733581185341e-2f);
+    pl = fmaf(pl, f, 2.4022242426872253e-1f);
+    pl = fmaf(pl, f, 6.931470036506653e-1f);
+    pl = fmaf(pl, f, 1.0f);
+    e = __uint_as_float(__float_as_uint(pl) + (__float_as_uint(tm) << 23));
+  }
+  return min_f32_raw(op * e, 0.99f);
+}
+
 // FAST_EXP: alpha = opacity * 2^(power * log2 e) on the hardware exponential (v_exp_f32, 1 ulp) instead of the oracle's
-// deterministic polynomial exp_det() -- 3 issue slots per pair of entries instead of 13.  The image is no longer bit-equal
+// deterministic polynomial exp_det() -- 2 issue slots per entry instead of 13.  The image is no longer bit-equal
 // to oracle/rasterizer_oracle.c but stays within 1e-5 relative of it (tests/test_gpu_rasterizer_fast.py); opt-in
 // (GR_RASTER_FAST_EXP flag of gr_raster_render_ex).
 // KEEP (the autograd forward, gr_raster_render_keep): out_color is followed in the same allocation by the per-pixel final
@@ -840,21 +874,18 @@ __device__ __forceinline__ float min_f32_raw(float a, float b) {  // fminf, same
 // concatenated list (0 = none) -- the state rasterizer_backward.hip starts from.  (No extra kernel argument: the
 // instances without KEEP keep their kernel-argument layout and compile to the instruction stream they had before.)
 template <bool FAST_EXP, bool KEEP = false>
-__global__ __launch_bounds__(BLOCK) void blend_kernel(
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void blend_kernel(
     int P, int W, int H, int nchunk, const DevView* __restrict__ views, const uint32_t* __restrict__ seg_off,
     const int32_t* __restrict__ point_list, const float4* __restrict__ rec, float* __restrict__ out_color,
     unsigned int list_cap) {
-  // One plane per field: the blend reads field f of two different entries into the two halves of a register pair
-  // (ds_read_b32 x 2), which is the operand layout of the packed fp32 instructions -- no register shuffling.
-  // (Plane stride 257 dwords: neither <= 255 nor a multiple of 64, so the compiler cannot fuse two fields of ONE entry
-  // into a ds_read2[st64]_b32 -- that would hand back exactly the wrong pairing.)
-  constexpr int PL = BLOCK + 1;
-  __shared__ float s_pl[10 * PL];
-  float* const s_px = s_pl, * const s_py = s_pl + PL, * const s_pc = s_pl + 2 * PL;          // centre, power cutoff
-  float* const s_cx = s_pl + 3 * PL, * const s_cy = s_pl + 4 * PL, * const s_cz = s_pl + 5 * PL;  // conic
-  float* const s_op = s_pl + 6 * PL;                                                          // opacity
-  float* const s_cr = s_pl + 7 * PL, * const s_cg = s_pl + 8 * PL, * const s_cb = s_pl + 9 * PL;  // colour
-  __shared__ unsigned short s_list[NCELL][BLOCK + 2];                   // byte offsets (4 * entry) into the planes
+  // One 40-byte record per entry, in three arrays, so that the walk reads an entry with two ds_read_b128 and one
+  // ds_read_b64 (10 LDS-array cycles per wave) instead of ten ds_read_b32 (20):
+  //   s_ga[e] = {px, py, conic x, conic z}   s_gb[e] = {conic y, opacity, power cutoff, red}   s_gc[e] = {green, blue}
+  // Entry e sits at byte 16 e of s_ga / s_gb and 8 e of s_gc.  (Two entries read by one lane group of a ds_read_b128
+  // share a bank only when their indices agree mod 16.)  Same 10 280 bytes as ten 257-entry planes: 8 workgroups per CU.
+  __shared__ float4 s_ga[BLOCK + 1], s_gb[BLOCK + 1];
+  __shared__ f32x2 s_gc[BLOCK + 1];
+  __shared__ unsigned short s_list[NCELL][BLOCK + 2];                   // byte offsets (16 * entry) into s_ga / s_gb
   __shared__ int s_cnt[NCELL][BLOCK / WAVE];      // per (cell, loading wave) counts
   __shared__ int s_alldone[BLOCK / WAVE];
   __shared__ int s_wpre[WAVE];                    // window of 64 chunks: inclusive prefix of this tile's segment lengths
@@ -873,13 +904,17 @@ __global__ __launch_bounds__(BLOCK) void blend_kernel(
   const int ly = (cell / (TILE / CELL)) * CELL + pin / CELL;
   const int pxi = blockIdx.x * TILE + lx, pyi = blockIdx.y * TILE + ly;
   const bool inside = pxi < W && pyi < H;
-  const float pfx = (float)pxi, pfy = (float)pyi;
+  const f32x2 pf = {(float)pxi, (float)pyi};
   const float tx0 = (float)(blockIdx.x * TILE), ty0 = (float)(blockIdx.y * TILE);
   const int tiles = gx * gy;
   const int64_t goff = (int64_t)v * P;
   bool done = !inside;
-  // entry BLOCK of every plane: the pad entry of odd-length lists.  Cutoff +inf: `power < pc` holds, it never blends.
-  if (tid < 10) s_pl[tid * PL + BLOCK] = tid == 2 ? INFINITY : 0.0f;
+  // entry BLOCK: the pad entry of odd-length lists.  Cutoff +inf: `power < pc` holds, it never blends.
+  if (tid == 0) {
+    s_ga[BLOCK] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    s_gb[BLOCK] = make_float4(0.0f, 0.0f, INFINITY, 0.0f);
+    s_gc[BLOCK] = f32x2{0.0f, 0.0f};
+  }
   float T = 1.0f, C0 = 0.f;
   f32x2 C12 = {0.f, 0.f};
   // The tile's list = its segments of chunk 0, 1, 2, ... (depth order).  64 chunks are looked up at a time (one wave:
@@ -948,16 +983,9 @@ __global__ __launch_bounds__(BLOCK) void blend_kernel(
       hy2 = cpr * r0.w;
       ctr_x = r0.x;
       ctr_y = r0.y;
-      s_px[tid] = r0.x;
-      s_py[tid] = r0.y;
-      s_pc[tid] = pc;
-      s_cx[tid] = co.x;
-      s_cy[tid] = co.y;
-      s_cz[tid] = co.z;
-      s_op[tid] = co.w;
-      s_cr[tid] = col.x;
-      s_cg[tid] = col.y;
-      s_cb[tid] = col.z;
+      s_ga[tid] = make_float4(r0.x, r0.y, co.x, co.z);
+      s_gb[tid] = make_float4(co.y, co.w, pc, col.x);
+      s_gc[tid] = f32x2{col.y, col.z};
     }
     float ex2[TILE / CELL], ey2[TILE / CELL];
     bool xin[TILE / CELL], yin[TILE / CELL];
@@ -992,55 +1020,40 @@ __global__ __launch_bounds__(BLOCK) void blend_kernel(
         tot_lane += n;
       }
       // lists are walked in pairs: pad an odd one with the never-hit entry
-      if (lw == 0 && (tot_lane & 1)) s_list[lane][tot_lane] = (unsigned short)(4 * BLOCK);
+      if (lw == 0 && (tot_lane & 1)) s_list[lane][tot_lane] = (unsigned short)(16 * BLOCK);
     }
 #pragma unroll
     for (int c = 0; c < NCELL; ++c) {
       const int base = __builtin_amdgcn_readlane(base_lane, c);
       const unsigned int rank = __builtin_amdgcn_mbcnt_hi((unsigned int)(reach[c] >> 32),
                                                           __builtin_amdgcn_mbcnt_lo((unsigned int)reach[c], 0u));
-      if (__builtin_amdgcn_inverse_ballot_w64(reach[c])) s_list[c][base + rank] = (unsigned short)(4 * tid);
+      if (__builtin_amdgcn_inverse_ballot_w64(reach[c])) s_list[c][base + rank] = (unsigned short)(16 * tid);
     }
     __syncthreads();
     // ---- blend: each 16-lane group walks its own list
     const int len_cell = __shfl(tot_lane, (BLOCK / WAVE) * lw + lane / (CELL * CELL));  // cell = 4 lw + lane / 16
     const int n_cell = done ? 0 : len_cell;
-    // Two list entries per step: everything up to alpha is evaluated for both at once with packed fp32 math
-    // (v_pk_fma/mul/add_f32 -- the same IEEE operations as the scalar sequence of the oracle, two per lane-slot);
-    // only the order-dependent tail (transmittance test, colour accumulation) runs entry by entry.
-    const unsigned short* lp = &s_list[cell][0];
+    // Two list entries per step, each read as {px, py, cx, cz} + {cy, op, pc, r} (+ {g, b} when it blends) and evaluated
+    // on its own registers: dx, dy, q, power, the exponential and alpha are the oracle's scalar sequence per entry (the
+    // compiler may pack the two entries' independent operations); only the order-dependent tail (transmittance test,
+    // colour accumulation) is serial.
+    // The next step's two offsets are read one step ahead (one 4-byte read per step; the row holds BLOCK + 2 of them,
+    // so the read after the last step stays inside it), and the step's record reads do not wait behind the list read.
+    const unsigned int* lp = reinterpret_cast<const unsigned int*>(&s_list[cell][0]);
+    unsigned int pair = lp[0];
     for (int i = 0; i < n_cell && !done; i += 2) {
-      const unsigned int o0 = lp[i], o1 = lp[i + 1];  // byte offsets of two list entries (an odd list ends with the pad entry)
-      const f32x2 dx = f32x2{lds_f32(s_px, o0), lds_f32(s_px, o1)} - pfx, dy = f32x2{lds_f32(s_py, o0), lds_f32(s_py, o1)} - pfy;
-      const f32x2 cx = {lds_f32(s_cx, o0), lds_f32(s_cx, o1)}, cy = {lds_f32(s_cy, o0), lds_f32(s_cy, o1)};
-      const f32x2 cz = {lds_f32(s_cz, o0), lds_f32(s_cz, o1)}, cw = {lds_f32(s_op, o0), lds_f32(s_op, o1)};
-      const float pc0 = lds_f32(s_pc, o0), pc1 = lds_f32(s_pc, o1);
-      const f32x2 q = __builtin_elementwise_fma(cx * dx, dx, (cz * dy) * dy);
-      const f32x2 power = __builtin_elementwise_fma(f32x2{-0.5f, -0.5f}, q, -((cy * dx) * dy));
-      f32x2 al;
-      if (FAST_EXP) {
-        const f32x2 t = power * 1.44269504088896341f;
-        al = cw * f32x2{__builtin_amdgcn_exp2f(t.x), __builtin_amdgcn_exp2f(t.y)};
-      } else {
-        // exp_det(), two at a time: 13 issue slots per pair (the Cephes form of rounds 1 - 5 took 20)
-        const f32x2 x = {max_f32_raw(power.x, -86.0f), max_f32_raw(power.y, -86.0f)};
-        const f32x2 l2e = {1.44269504088896341f, 1.44269504088896341f}, magic = {12582912.0f, 12582912.0f};
-        const f32x2 t = x * l2e;
-        const f32x2 tm = t + magic;
-        const f32x2 nf = tm - magic;
-        const f32x2 f = __builtin_elementwise_fma(x, l2e, -nf);
-        f32x2 pl = {1.3264815788716078e-3f, 1.3264815788716078e-3f};
-        pl = __builtin_elementwise_fma(pl, f, f32x2{9.671512059867382e-3f, 9.671512059867382e-3f});
-        pl = __builtin_elementwise_fma(pl, f, f32x2{5.550733581185341e-2f, 5.550733581185341e-2f});
-        pl = __builtin_elementwise_fma(pl, f, f32x2{2.4022242426872253e-1f, 2.4022242426872253e-1f});
-        pl = __builtin_elementwise_fma(pl, f, f32x2{6.931470036506653e-1f, 6.931470036506653e-1f});
-        pl = __builtin_elementwise_fma(pl, f, f32x2{1.0f, 1.0f});
-        al = cw * f32x2{__uint_as_float(__float_as_uint(pl.x) + (__float_as_uint(tm.x) << 23)),
-                        __uint_as_float(__float_as_uint(pl.y) + (__float_as_uint(tm.y) << 23))};
-      }
-      const float alpha0 = min_f32_raw(al.x, 0.99f), alpha1 = min_f32_raw(al.y, 0.99f);
-      const bool ok0 = !(power.x > 0.0f) && !(power.x < pc0) && !(alpha0 < 1.0f / 255.0f);
-      const bool ok1 = !(power.y > 0.0f) && !(power.y < pc1) && !(alpha1 < 1.0f / 255.0f);
+      const unsigned int o0 = pair & 0xffffu, o1 = pair >> 16;  // byte offsets of two entries (an odd list ends with the pad entry)
+      pair = lp[i / 2 + 1];
+      const float4 a0 = lds_at(s_ga, o0), b0 = lds_at(s_gb, o0);
+      const float4 a1 = lds_at(s_ga, o1), b1 = lds_at(s_gb, o1);
+      // red is used only where the entry blends: without this the compiler splits {cy, op, pc, r} into a ds_read_b96
+      // (8 LDS cycles) and a ds_read_b32 under the branch (2 more) instead of one ds_read_b128 (4)
+      asm volatile("" ::"v"(b0.w), "v"(b1.w));
+      float power0, power1;
+      const float alpha0 = entry_alpha<FAST_EXP>(a0, b0.x, b0.y, pf, power0);
+      const float alpha1 = entry_alpha<FAST_EXP>(a1, b1.x, b1.y, pf, power1);
+      const bool ok0 = !(power0 > 0.0f) && !(power0 < b0.z) && !(alpha0 < 1.0f / 255.0f);
+      const bool ok1 = !(power1 > 0.0f) && !(power1 < b1.z) && !(alpha1 < 1.0f / 255.0f);
       // A pixel that saturates leaves the walk through the loop condition, not through a `break`: the wave's control flow
       // stays one counted loop with two predicated regions.
       if (ok0) {
@@ -1049,10 +1062,10 @@ __global__ __launch_bounds__(BLOCK) void blend_kernel(
           done = true;
         } else {
           const float w = alpha0 * T;
-          C0 = fmaf(lds_f32(s_cr, o0), w, C0);
-          C12 = __builtin_elementwise_fma(f32x2{lds_f32(s_cg, o0), lds_f32(s_cb, o0)}, f32x2{w, w}, C12);
+          C0 = fmaf(b0.w, w, C0);
+          C12 = __builtin_elementwise_fma(lds_at(s_gc, o0 / 2), f32x2{w, w}, C12);
           T = test_T;
-          if (KEEP) last = batch_base + (int)(o0 / 4) + 1;
+          if (KEEP) last = batch_base + (int)(o0 / 16) + 1;
         }
       }
       if (ok1 && !done) {
@@ -1061,10 +1074,10 @@ __global__ __launch_bounds__(BLOCK) void blend_kernel(
           done = true;
         } else {
           const float w = alpha1 * T;
-          C0 = fmaf(lds_f32(s_cr, o1), w, C0);
-          C12 = __builtin_elementwise_fma(f32x2{lds_f32(s_cg, o1), lds_f32(s_cb, o1)}, f32x2{w, w}, C12);
+          C0 = fmaf(b1.w, w, C0);
+          C12 = __builtin_elementwise_fma(lds_at(s_gc, o1 / 2), f32x2{w, w}, C12);
           T = test_T;
-          if (KEEP) last = batch_base + (int)(o1 / 4) + 1;
+          if (KEEP) last = batch_base + (int)(o1 / 16) + 1;
         }
       }
     }
