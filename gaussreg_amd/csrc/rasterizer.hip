@@ -112,15 +112,9 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   const float p[3] = {means3D[3 * (int64_t)i], means3D[3 * (int64_t)i + 1], means3D[3 * (int64_t)i + 2]};
   const float opacity = opacities[i];
   float c6[6];
-  float sc[3], rot[4];
   if (HAS_COV) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * (int64_t)i + k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sc[k] = scales[3 * (int64_t)i + k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rot[k] = rotations[4 * (int64_t)i + k];
   }
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
   const float* sh = HAS_SH ? shs + (int64_t)i * M * 3 : nullptr;
@@ -129,6 +123,7 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
 #pragma unroll
     for (int k = 0; k < 3; ++k) cpre[k] = colors_precomp[3 * (int64_t)i + k];
   }
+  float4* wrec = s_rec[threadIdx.x / WAVE];
   float mod_prev = 0.f;
   bool have_cov = HAS_COV;
   for (int v = 0; v < V; ++v) {
@@ -136,10 +131,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     const int64_t o = (int64_t)v * P + i;
     int out_radius = 0;
     uint32_t out_field = 0u, out_rect = 0u;  // culled: depth field 0
-    float out_depth = 0.f, out_sxx = INFINITY, out_syy = INFINITY;
+    float out_depth = 0.f, out_sxx = INFINITY, out_syy = INFINITY, out_kc = 0.f;
     float2 out_xy = make_float2(0.f, 0.f);
     float4 out_co = make_float4(0.f, 0.f, 0.f, 0.f);
-    float4 out_rgb = make_float4(0.f, 0.f, 0.f, 0.f);
+    bool shade = false;
+    float rgb[3] = {0.f, 0.f, 0.f};
     float pv[3];
     xform4x3(cam.view, p, pv);
     if (pv[2] > 0.2f) {
@@ -148,6 +144,12 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       const float pw = 1.0f / (ph[3] + 0.0000001f);
       const float pprojx = ph[0] * pw, pprojy = ph[1] * pw;
       if (!HAS_COV && (!have_cov || cam.scale_mod != mod_prev)) {
+        // scales / rotations are read again here rather than held across the view loop: cov3D changes only with scale_mod
+        float sc[3], rot[4];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) sc[k] = scales[3 * (int64_t)i + k];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rot[k] = rotations[4 * (int64_t)i + k];
         cov3d_from_scale_rot(sc, cam.scale_mod, rot, c6);
         have_cov = true;
         mod_prev = cam.scale_mod;
@@ -167,34 +169,31 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
         get_rect(px, py, (int)my_radius, gx, gy, rmin, rmax);
         const int ntile = (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]);
         if (ntile != 0) {
-          float rgb[3];
-          if (HAS_SH) {
-            if (SH16 && LATE) {
-              const float4* s4 = reinterpret_cast<const float4*>(shs + (int64_t)i * 48);
+          shade = true;
+          if (HAS_SH && SH16 && LATE) {
+            // one camera: the coefficients are loaded here and used at once -- ahead of this view's stores, which a load
+            // issued after them would wait for
+            const float4* s4 = reinterpret_cast<const float4*>(shs + (int64_t)i * 48);
 #pragma unroll
-              for (int jj = 0; jj < 12; ++jj) {
-                const float4 t4 = s4[jj];
-                shr[4 * jj] = t4.x;
-                shr[4 * jj + 1] = t4.y;
-                shr[4 * jj + 2] = t4.z;
-                shr[4 * jj + 3] = t4.w;
-              }
+            for (int jj = 0; jj < 12; ++jj) {
+              const float4 t4 = s4[jj];
+              shr[4 * jj] = t4.x;
+              shr[4 * jj + 1] = t4.y;
+              shr[4 * jj + 2] = t4.z;
+              shr[4 * jj + 3] = t4.w;
             }
-            if (SH16) sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return shr[k * 3 + c]; }, rgb);
-            else sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return sh[k * 3 + c]; }, rgb);
-          } else {
-            rgb[0] = cpre[0]; rgb[1] = cpre[1]; rgb[2] = cpre[2];
+            sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return shr[k * 3 + c]; }, rgb);
           }
           out_depth = pv[2];
           out_radius = (int)my_radius;
           out_xy = make_float2(px, py);
           out_co = make_float4(cv[2] * det_inv, -cv[1] * det_inv, cv[0] * det_inv, opacity);
-          // rgb.w: k such that |d|^2 > |pc| * k  ==>  fp32 power < pc for any cutoff pc < 0 (blend
+          // kc: k such that |d|^2 > |pc| * k  ==>  fp32 power < pc for any cutoff pc < 0 (blend
           // cell culling).  power <= -|d|^2 (0.5/l1 - 2e-6): the 2e-6 covers the fp32 evaluation
           // error of the quadratic form given lambda_min(cov) >= 0.3 (the +0.3 dilation).
           const bool cullable = det > 0.0f && l2 >= 0.29f && l1 < 1.0e4f;
           const float kc = cullable ? 1.001f / (0.5f / l1 - 2.0e-6f) : INFINITY;
-          out_rgb = make_float4(rgb[0], rgb[1], rgb[2], kc);
+          out_kc = kc;
           // Tile rectangle actually emitted: the reference square (radius = ceil(3 sigma_max)) intersected with the
           // bounding box of the region where alpha can reach 1/255.  A pixel contributes only if fp32 power >= pc
           // (pc as in the blend, with margin); inside the cutoff circle rc2 the fp32 quadratic form is within
@@ -236,6 +235,11 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
       dfield[o] = out_field;
       rect_raw[o] = out_rect;
     }
+    // Record pieces 0, 1 and 3 go to LDS before the colour is evaluated: the SH coefficients are the largest live set of
+    // the loop, and no other record value is held in registers beside them.
+    wrec[0 * REC_PLANE + lane] = make_float4(out_xy.x, out_xy.y, out_sxx, out_syy);
+    wrec[1 * REC_PLANE + lane] = out_co;
+    wrec[3 * REC_PLANE + lane] = make_float4(__int_as_float(out_radius), out_depth, 0.f, 0.f);  // wide-rectangle fallback only
     if (key_mm != nullptr) {  // the block's key range of this view, for the bucket sort (depth_sort.hip)
       const uint32_t fld = valid ? out_field : 0u;
       const int mn = wave_min_i32_dpp(fld != 0u ? (int)fld : 0x7fffffff), mx = wave_max_i32_dpp((int)fld);
@@ -248,16 +252,20 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
         key_mm[(int64_t)v * gridDim.x + blockIdx.x] = make_int2(bmn, bmx);
       }
     }
+    if (shade && !(HAS_SH && SH16 && LATE)) {
+      if (HAS_SH) {
+        if (SH16) sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return shr[k * 3 + c]; }, rgb);
+        else sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return sh[k * 3 + c]; }, rgb);
+      } else {
+        rgb[0] = cpre[0]; rgb[1] = cpre[1]; rgb[2] = cpre[2];
+      }
+    }
+    wrec[2 * REC_PLANE + lane] = make_float4(rgb[0], rgb[1], rgb[2], out_kc);
     // The wave's 64 records (4 KB, contiguous) leave through LDS: lane l stores piece l % 4 of record 16 k + l / 4 in
     // store k, so every store instruction covers whole lines.  (Each lane writing its own record piece by piece costs four
     // partial-line writes per record: measured 0.26 ms of the 0.77 ms kernel at 32 views.)  Culled Gaussians are never
     // gathered: their 64-B line is not touched at all.
     const unsigned long long vis = __ballot(valid && out_radius > 0);
-    float4* wrec = s_rec[threadIdx.x / WAVE];
-    wrec[0 * REC_PLANE + lane] = make_float4(out_xy.x, out_xy.y, out_sxx, out_syy);
-    wrec[1 * REC_PLANE + lane] = out_co;
-    wrec[2 * REC_PLANE + lane] = out_rgb;
-    wrec[3 * REC_PLANE + lane] = make_float4(__int_as_float(out_radius), out_depth, 0.f, 0.f);  // wide-rectangle fallback only
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
