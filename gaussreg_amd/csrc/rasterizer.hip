@@ -304,8 +304,10 @@ __global__ __launch_bounds__(256) void full_keys_kernel(int64_t n, const float4*
 // chunk order = depth order, so it sees exactly what a stable sort of (tile, depth-rank) keys would give, but no key is
 // ever materialised and every global write is a full coalesced line (scattering 4-byte ids straight into per-tile lists
 // was measured first: 62 M partial-line writes per 32 views cost 1.1 ms in the L2 alone).
-//   count    a workgroup owns a chunk, histograms its tiles in LDS -> chunk_cnt, chunk_total
-//   scan     chunk totals -> chunk bases (per view); per chunk an exclusive scan over the tiles -> seg_off
+//   count    a few views: a workgroup owns a chunk, histograms its tiles in LDS -> chunk_cnt, chunk_total; many views:
+//            only the chunk totals (chunk_total_kernel)
+//   scan     chunk totals -> chunk bases (per view); a few views: per chunk an exclusive scan over the tiles -> seg_off
+//            (many views: the scatter scans the tile counts it builds anyway and writes its own row of seg_off)
 //   scatter  a workgroup owns a chunk; wave w owns a quarter of its Gaussians and a private cursor per tile in LDS
 //            (segment start + the earlier waves' counts).  64 Gaussians (lanes) per step:
 //              small rectangles (<= 8 x 8 tiles, wave-uniform test): with M = 2 / 4 / 8 >= the largest side, a rectangle
@@ -335,6 +337,13 @@ __device__ __forceinline__ bool bin_block(int V, int nchunk, int& v, int& c) {
   return true;
 }
 inline int bin_grid(int V, int nchunk) { return V >= 8 ? 8 * ((V + 7) / 8) * nchunk : V * nchunk; }
+// a few views per call (short chunk rows): tile_count_kernel + seg_scan_kernel<true> write seg_off; otherwise only the
+// chunk totals are counted and scanned, and the scatter writes seg_off itself
+inline bool bin_scans_self(int nchunk, int V) { return !(nchunk <= SCAN_SINGLE_ROW && V <= 4); }
+// many views: resident scatter workgroups per CU that the LDS staging block is sized for (measured at 1 M Gaussians,
+// 640 x 480, 32 views: 4 / 5 / 6 / 8 -> 308 / 306 / 278 / 370 us; at 6, 2 % of the chunks take the direct path)
+constexpr int SCATTER_WGS = 6;
+constexpr int WIDE_T = 1024;  // threads per scatter workgroup for a few views per call
 
 __global__ __launch_bounds__(BIN_T) void tile_count_kernel(int P, int V, int gx, int gy, int nchunk,
                                                            const int32_t* __restrict__ nvis,
@@ -377,6 +386,43 @@ __global__ __launch_bounds__(BIN_T) void tile_count_kernel(int P, int V, int gx,
   uint16_t* dst = chunk_cnt + ((int64_t)v * nchunk + c) * tiles;
   // a tile can appear at most once per Gaussian: counts <= BIN_CHUNK < 65536
   for (int T = threadIdx.x; T < tiles; T += BIN_T) dst[T] = (uint16_t)s_hist[T];
+  if (threadIdx.x == 0) {
+    int tot = 0;
+    for (int i = 0; i < BIN_T / WAVE; ++i) tot += s_wsum[i];
+    chunk_total[v * nchunk + c] = tot;
+  }
+}
+
+// many views per call: only the instance total of every (view, chunk) -- no tile histogram.  The scatter counts the tiles
+// of its chunk anyway and scans them itself (tile_scatter_kernel SEG_SELF_SCAN); it needs nothing but the chunk bases.
+__global__ __launch_bounds__(BIN_T) void chunk_total_kernel(int P, int V, int gx, int gy, int nchunk,
+                                                            const int32_t* __restrict__ nvis,
+                                                            const uint32_t* __restrict__ rects,
+                                                            const int32_t* __restrict__ ids,
+                                                            const float4* __restrict__ rec,
+                                                            int32_t* __restrict__ chunk_total) {
+  __shared__ int s_wsum[BIN_T / WAVE];
+  int v, c;
+  if (!bin_block(V, nchunk, v, c)) return;
+  const int64_t vbase = (int64_t)v * P;
+  const int nv = nvis[v];
+  int mine = 0;
+  uint32_t rr[BIN_CHUNK / BIN_T];
+#pragma unroll
+  for (int it = 0; it < BIN_CHUNK / BIN_T; ++it) {
+    const int t = c * BIN_CHUNK + it * BIN_T + threadIdx.x;
+    rr[it] = t < nv ? rects[vbase + t] : 0u;
+  }
+#pragma unroll
+  for (int it = 0; it < BIN_CHUNK / BIN_T; ++it) {
+    const int t = c * BIN_CHUNK + it * BIN_T + threadIdx.x;
+    const uint32_t r = rr[it];
+    int x0, y0, w, h;
+    if (r != 0u && rect_decode(r, r == RECT_MARKER26 ? ids[vbase + t] : 0, vbase, rec, gx, gy, x0, y0, w, h)) mine += w * h;
+  }
+  const int wsum = wave_sum_i32_dpp(mine);
+  if ((threadIdx.x & (WAVE - 1)) == 0) s_wsum[threadIdx.x / WAVE] = wsum;
+  __syncthreads();
   if (threadIdx.x == 0) {
     int tot = 0;
     for (int i = 0; i < BIN_T / WAVE; ++i) tot += s_wsum[i];
@@ -479,17 +525,26 @@ __global__ __launch_bounds__(256) void seg_scan_kernel(int V, int tiles, int nch
 // TT = threads per workgroup: 256 (four waves, each a quarter of the chunk) for many views per call; 1024 for a few views,
 // where the launch has fewer workgroups than the chip has CUs and a workgroup's walk through its chunk IS the kernel's
 // duration (16 waves, an eighth of the steps each: 33 -> 12 us per one-camera frame)
-// SELF_SEG (a few views per call, behind the bucket depth sort): no count / scan launch ran before this one.  The chunk
-// totals came out of the sort (chunk_total: raw, per (view, chunk)); every workgroup sums the ones in front of its own,
-// scans the tile counts it has to build anyway and WRITES its row of seg_off for the blend; the first chunk of a view
-// reports the view's total and largest chunk to the host (see seg_scan_kernel<true>, whose job this is otherwise).
+// SEG says where the chunk's place in the list and its segment starts come from:
+//   SEG_READ       (a few views per call, plain path) tile_count_kernel + seg_scan_kernel wrote every row of seg_off
+//   SEG_SELF_RAW   (a few views per call, behind the bucket depth sort): no count / scan launch ran before this one.  The
+//                  chunk totals came out of the sort (chunk_total: raw, per (view, chunk)); every workgroup sums the ones in
+//                  front of its own, and the first chunk of a view reports the view's total and largest chunk to the host
+//                  (see seg_scan_kernel<true>, whose job this is otherwise)
+//   SEG_SELF_SCAN  (many views per call): chunk_total_kernel + exclusive_scan_i32 left the raw totals, the chunk bases
+//                  inside every view (chunk_total + V * nchunk) and the view totals
+// In both SELF modes the workgroup scans the tile counts it has to build anyway and WRITES its row of seg_off for the blend.
+constexpr int SEG_READ = 0, SEG_SELF_RAW = 1, SEG_SELF_SCAN = 2;
 struct SelfSeg {
   const int32_t* chunk_total;
   int32_t* totals;
   int32_t* mail;
   int mail_seq;
 };
-template <bool LANE_ORDERED, int TT, bool SELF_SEG = false>
+// The per-wave cursors are 16-bit, two tiles to an LDS word (rows of an even number of tiles): positions inside the chunk,
+// which holds at most 65 535 instances -- a larger one (block-uniform `big`) keeps positions inside the tile's segment and
+// writes at seg_off[tile] + position.  A cursor never carries into its neighbour: it stays below the chunk (segment) end.
+template <bool LANE_ORDERED, int TT, int SEG = SEG_READ>
 __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, int gy, int nchunk, int tile_bits,
                                                              int stage_cap, const int32_t* __restrict__ nvis,
                                                              const uint32_t* __restrict__ rects,
@@ -500,11 +555,13 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
                                                              SelfSeg self) {
   // list_cap: entries the point list holds.  A speculative launch (gr_raster_forward) sizes the list before the instance
   // count is known: a chunk that would end past it writes nothing (the host then repeats the render with a larger list)
-  extern __shared__ unsigned int s_cur[];  // [waves][tiles] counts -> cursors, then [stage_cap] staged chunk-local indices
+  extern __shared__ unsigned int s_cur[];  // [waves][row] 16-bit counts -> cursors, then [stage_cap] staged chunk-local indices
   constexpr int NW = TT / WAVE, CW = BIN_CHUNK / NW;
+  constexpr bool SELF = SEG != SEG_READ;
   int v, c;
   if (!bin_block(V, nchunk, v, c)) return;
   const int tiles = gx * gy;
+  const int row = (tiles + 1) & ~1;  // halfwords per wave row
   uint32_t* seg = seg_off + ((int64_t)v * nchunk + c) * (tiles + 1);
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   // the wave's rectangles and ids, requested up front and before anything else is waited for (on clamped positions; what
@@ -525,7 +582,7 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
   __shared__ unsigned int s_carry;
   unsigned int chunk_begin;
   int total;
-  if (SELF_SEG) {
+  if (SEG == SEG_SELF_RAW) {
     const int me = v * nchunk + c;  // everything in front belongs to earlier views / chunks
     int part = 0;
     for (int i = threadIdx.x; i < me; i += TT) part += self.chunk_total[i];
@@ -562,24 +619,33 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
         }
       }
     }
-    if (total == 0) {  // an empty row for the blend
-      for (int T = threadIdx.x; T <= tiles; T += TT) seg[T] = chunk_begin;
-      return;
-    }
-    // (a chunk that would end past the list still counts and scans: the render that repeats this frame with a larger list
-    // finds every row of seg_off in place; it stops before it writes any entry)
+  } else if (SEG == SEG_SELF_SCAN) {
+    // (V <= MAX_VIEWS: the views in front are a few scalar loads)
+    unsigned int front = (unsigned int)self.chunk_total[(int64_t)V * nchunk + v * nchunk + c];
+    for (int u = 0; u < v; ++u) front += (unsigned int)self.totals[u];
+    chunk_begin = front;
+    total = self.chunk_total[v * nchunk + c];
   } else {
     chunk_begin = seg[0];
     total = (int)(seg[tiles] - chunk_begin);
     if (total == 0 || seg[tiles] > list_cap) return;  // block-uniform
   }
-  const bool staged = total <= stage_cap;
-  unsigned int* my = s_cur + wv * tiles;
+  if (SELF && total == 0) {  // an empty row for the blend
+    for (int T = threadIdx.x; T <= tiles; T += TT) seg[T] = chunk_begin;
+    return;
+  }
+  // (SELF: a chunk that would end past the list still counts and scans: the render that repeats this frame with a larger
+  // list finds every row of seg_off in place; it stops before it writes any entry)
+  const bool big = total > 0xffff;
+  const bool staged = !big && total <= stage_cap;
+  unsigned int* myw = s_cur + wv * (row / 2);  // this wave's cursor row, two tiles per word
+  unsigned short* const cur16 = reinterpret_cast<unsigned short*>(s_cur);
+  unsigned short* my16 = cur16 + wv * row;
   // staged entries are 16-bit positions inside the chunk (BIN_CHUNK <= 65536); the ids are looked up on the way out
-  unsigned short* stage = reinterpret_cast<unsigned short*>(s_cur + NW * tiles);
+  unsigned short* stage = reinterpret_cast<unsigned short*>(s_cur + NW * (row / 2));
   // (elist_cap > 0) per wave: the (owner lane, tile) words of one 64-Gaussian step, behind the staging block
-  unsigned int* elist = s_cur + NW * tiles + (stage_cap + 1) / 2 + wv * elist_cap;
-  for (int T = threadIdx.x; T < NW * tiles; T += TT) s_cur[T] = 0u;
+  unsigned int* elist = s_cur + NW * (row / 2) + (stage_cap + 1) / 2 + wv * elist_cap;
+  for (int T = threadIdx.x; T < NW * (row / 2); T += TT) s_cur[T] = 0u;
   __syncthreads();
   const int w_end = min(nv, w_begin + CW);
 #pragma unroll
@@ -588,18 +654,42 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
     rr[j] = t < w_end ? rr[j] : 0u;  // (past the view's visible count the arrays hold leftovers)
     ii[j] = t < w_end ? ii[j] : 0;
   }
-  // ---- phase A: this wave's tile counts
+  auto count = [&](int tile) { atomicAdd(&myw[tile >> 1], 1u << ((tile & 1) * 16)); };
+  // ---- phase A: this wave's tile counts, with the residue-class walk of phase C (a lane issues at most one tile per class)
+  // instead of a loop per lane over its own rectangle, which ran every wave for its largest rectangle
 #pragma unroll
   for (int j = 0; j < CW / WAVE; ++j) {
     const uint32_t r = rr[j];
-    int x0, y0, w, h;
-    if (r != 0u && rect_decode(r, ii[j], vbase, rec, gx, gy, x0, y0, w, h))
+    int x0 = 0, y0 = 0, w = 0, h = 0;
+    if (r != 0u && !rect_decode(r, ii[j], vbase, rec, gx, gy, x0, y0, w, h)) w = h = 0;
+    const int maxd = wave_max_i32_dpp(max(w, h));
+    auto cwalk = [&](auto mtag) {
+      constexpr int M = decltype(mtag)::value;
+#pragma unroll
+      for (int ry = 0; ry < M; ++ry) {
+        const int dy = (ry - y0) & (M - 1);
+        const int rowbase = (y0 + dy) * gx + x0;
+#pragma unroll
+        for (int rx = 0; rx < M; ++rx) {
+          const int dx = (rx - x0) & (M - 1);
+          if (dy < h && dx < w) count(rowbase + dx);
+        }
+      }
+    };
+    if (maxd == 0) continue;
+    if (TT == WIDE_T) {  // (one camera: the walk measured slower there, 5 390 -> 5 260 views/s)
       for (int y = y0; y < y0 + h; ++y)
-        for (int x = x0; x < x0 + w; ++x) atomicAdd(&my[y * gx + x], 1u);
+        for (int x = x0; x < x0 + w; ++x) count(y * gx + x);
+    } else if (maxd <= 2) cwalk(std::integral_constant<int, 2>{});
+    else if (maxd <= 4) cwalk(std::integral_constant<int, 4>{});
+    else if (maxd <= 8) cwalk(std::integral_constant<int, 8>{});
+    else
+      for (int y = y0; y < y0 + h; ++y)
+        for (int x = x0; x < x0 + w; ++x) count(y * gx + x);
   }
   __syncthreads();
-  // ---- phase B: counts -> cursors (chunk-local when staged, global otherwise)
-  if (SELF_SEG) {
+  // ---- phase B: counts -> cursors (chunk-local; segment-local for a big chunk)
+  if (SELF) {
     // the segment starts are this workgroup's own exclusive scan over the tiles of the counts it just made
     if (threadIdx.x == 0) s_carry = 0u;
     __syncthreads();
@@ -609,7 +699,7 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
       int n_all = 0;
 #pragma unroll
       for (int w2 = 0; w2 < NW; ++w2) {
-        cw[w2] = T < tiles ? s_cur[w2 * tiles + T] : 0u;
+        cw[w2] = T < tiles ? cur16[w2 * row + T] : 0u;
         n_all += (int)cw[w2];
       }
       const int incl = wave_incl_scan_add_dpp(n_all);
@@ -619,10 +709,10 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
       for (int w2 = 0; w2 < wv; ++w2) before += (unsigned int)s_red[0][w2];
       if (T < tiles) {
         seg[T] = chunk_begin + before;
-        unsigned int run = before + (staged ? 0u : chunk_begin);
+        unsigned int run = big ? 0u : before;
 #pragma unroll
         for (int w2 = 0; w2 < NW; ++w2) {
-          s_cur[w2 * tiles + T] = run;
+          cur16[w2 * row + T] = (unsigned short)run;
           run += cw[w2];
         }
       }
@@ -634,21 +724,27 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
     if (chunk_begin + (unsigned int)total > list_cap) return;  // block-uniform
   } else {
     for (int T = threadIdx.x; T < tiles; T += TT) {
-      unsigned int run = seg[T] - (staged ? chunk_begin : 0u);
+      unsigned int run = big ? 0u : seg[T] - chunk_begin;
 #pragma unroll
       for (int w2 = 0; w2 < NW; ++w2) {
-        const unsigned int n = s_cur[w2 * tiles + T];
-        s_cur[w2 * tiles + T] = run;
+        const unsigned int n = cur16[w2 * row + T];
+        cur16[w2 * row + T] = (unsigned short)run;
         run += n;
       }
     }
   }
-  __syncthreads();
+  __syncthreads();  // (also orders this workgroup's seg_off stores before a big chunk's reads of them)
   // ---- phase C
-  // two typed stores under a block-uniform branch (a generic pointer would turn the LDS case into flat_store)
-  auto put = [&](unsigned int pos, int local, int val) {
+  // typed stores under a block-uniform branch (a generic pointer would turn the LDS case into flat_store)
+  auto put = [&](unsigned int tile, unsigned int pos, int local, int val) {
     if (staged) stage[pos] = (unsigned short)local;
-    else point_list[pos] = val;
+    else if (!big) point_list[chunk_begin + pos] = val;
+    else point_list[seg[tile] + pos] = val;
+  };
+  // LANE_ORDERED: one ds_add_rtn_u32 on the word of the tile's cursor; the other half of the word is another tile's
+  auto bump = [&](unsigned int tile) -> unsigned int {
+    const unsigned int sh = (tile & 1u) * 16u;
+    return (atomicAdd(&myw[tile >> 1], 1u << sh) >> sh) & 0xffffu;
   };
   const unsigned long long lt = (1ull << lane) - 1ull;
   // (rolled: the body is large; the preloaded values move down one register per step instead of being indexed)
@@ -685,11 +781,11 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
               const int dx = (rx - x0) & (M - 1);
               act[rx] = vy && dx < w;
               pos[rx] = 0u;
-              if (act[rx]) pos[rx] = atomicAdd(&my[rowbase + dx], 1u);
+              if (act[rx]) pos[rx] = bump((unsigned int)(rowbase + dx));
             }
 #pragma unroll
             for (int rx = 0; rx < M; ++rx)
-              if (act[rx]) put(pos[rx], t - c * BIN_CHUNK, id);
+              if (act[rx]) put((unsigned int)(rowbase + ((rx - x0) & (M - 1))), pos[rx], t - c * BIN_CHUNK, id);
           } else {
             for (int rx = 0; rx < M; ++rx) {
               const int dx = (rx - x0) & (M - 1);
@@ -703,9 +799,9 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
                 peers &= one ? bal : ~bal;
               }
               if (act) {
-                const unsigned int base = my[tile];
-                put(base + (unsigned int)__popcll(peers & lt), t - c * BIN_CHUNK, id);
-                if ((peers >> lane) == 1ull) my[tile] = base + (unsigned int)__popcll(peers);  // last lane of the group
+                const unsigned int base = my16[tile];
+                put(tile, base + (unsigned int)__popcll(peers & lt), t - c * BIN_CHUNK, id);
+                if ((peers >> lane) == 1ull) my16[tile] = (unsigned short)(base + (unsigned int)__popcll(peers));  // last lane
               }
               __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
               __builtin_amdgcn_wave_barrier();
@@ -746,7 +842,7 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
           const int oid = __shfl(id, owner, WAVE);
           const int olocal = t0 + owner - c * BIN_CHUNK;
           if (LANE_ORDERED) {
-            if (act) put(atomicAdd(&my[tile], 1u), olocal, oid);
+            if (act) put(tile, bump(tile), olocal, oid);
           } else {
             unsigned long long peers = __ballot(act);
             for (int bit = 0; bit < tile_bits; ++bit) {
@@ -755,9 +851,9 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
               peers &= one ? bal : ~bal;
             }
             if (act) {
-              const unsigned int base = my[tile];
-              put(base + (unsigned int)__popcll(peers & lt), olocal, oid);
-              if ((peers >> lane) == 1ull) my[tile] = base + (unsigned int)__popcll(peers);  // last lane of the group
+              const unsigned int base = my16[tile];
+              put(tile, base + (unsigned int)__popcll(peers & lt), olocal, oid);
+              if ((peers >> lane) == 1ull) my16[tile] = (unsigned short)(base + (unsigned int)__popcll(peers));  // last lane
             }
           }
           __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -776,13 +872,14 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
         for (int y = 0; y < sh; ++y)
           for (int xb = 0; xb < sw; xb += WAVE)
             if (xb + lane < sw) {
-              unsigned int* slot = &my[(sy + y) * gx + sx + xb + lane];
+              const unsigned int tile = (unsigned int)((sy + y) * gx + sx + xb + lane);
               if (LANE_ORDERED) {
-                put(atomicAdd(slot, 1u), t0 + j - c * BIN_CHUNK, sid);
+                put(tile, bump(tile), t0 + j - c * BIN_CHUNK, sid);
               } else {
-                const unsigned int pos = *slot;  // distinct tiles: no two lanes share a slot here
-                *slot = pos + 1u;
-                put(pos, t0 + j - c * BIN_CHUNK, sid);
+                // distinct tiles: no two lanes share a slot here (but two may share a word: a 16-bit store each)
+                const unsigned int pos = my16[tile];
+                my16[tile] = (unsigned short)(pos + 1u);
+                put(tile, pos, t0 + j - c * BIN_CHUNK, sid);
               }
             }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1318,7 +1415,7 @@ struct Deferred {
   bool by_mail;            // out: which of the two ways this frame took
   bool bucket_sort;        // in: take the four-launch depth sort
   bool self_seg;           // out: the depth sort left the chunk totals and nothing else was launched -- the scatter of this
-                           // frame scans its own segments and mails the counts (tile_scatter_kernel SELF_SEG)
+                           // frame scans its own segments and mails the counts (tile_scatter_kernel SEG_SELF_RAW)
 };
 
 // defer_ev != nullptr: everything is enqueued, the read-back of the counts is followed by this event instead of a stream
@@ -1418,7 +1515,7 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
       KernelTimer timer("raster_depth_sort", stream);
       // visible Gaussians of every view in depth order (ties: Gaussian id): ids -> order_b, rectangles -> rects
       const bool msd_now = msd && buckets && key_bits == KEY_DEPTH_BITS;
-      // ... and with the mailbox: no count / scan launch either, the scatter does both (its SELF_SEG variant)
+      // ... and with the mailbox: no count / scan launch either, the scatter does both (its SEG_SELF_RAW variant)
       const bool self_seg = msd_now && defer_ev != nullptr && defer_ev->mail != nullptr && nchunk <= SCAN_SINGLE_ROW &&
                             num_views <= 4;
       const DepthSortTotals ct{g.chunk_total, BIN_CHUNK, nchunk, g.rec, gx, gy};
@@ -1435,17 +1532,17 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
     }
     {
       KernelTimer timer("raster_bin", stream);
-      if (tiles * sizeof(unsigned int) > 64 * 1024)
-        GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_count_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T),
-                         tiles * sizeof(unsigned int), stream, (int)P, num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b,
-                         g.rec, g.chunk_cnt, g.chunk_total);
       // chunk bases inside each view (+ the per-view totals R_v and the largest chunk total, which sizes the scatter's
-      // staging block), then every chunk's per-tile segment starts
+      // staging block), and every chunk's per-tile segment starts: by the count / scan launches for a few views, by the
+      // scatter itself otherwise
       const bool short_rows = nchunk <= SCAN_SINGLE_ROW;  // one launch does scan, totals and maxima
-      const bool self_scan = short_rows && num_views <= 4;  // ... or none at all: seg_scan_kernel<true> sums what it needs
-      if (self_scan) {
+      if (!bin_scans_self(nchunk, num_views)) {  // ... or none at all: seg_scan_kernel<true> sums what it needs
+        if (tiles * sizeof(unsigned int) > 64 * 1024)
+          GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_count_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T),
+                           tiles * sizeof(unsigned int), stream, (int)P, num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b,
+                           g.rec, g.chunk_cnt, g.chunk_total);
         const bool by_mail = defer_ev != nullptr && defer_ev->mail != nullptr;
         hipLaunchKernelGGL(seg_scan_kernel<true>, dim3((unsigned)(num_views * nchunk)), blk, 0, stream, num_views, tiles, nchunk,
                            g.chunk_cnt, g.chunk_total, g.totals, g.seg_off, by_mail ? const_cast<int32_t*>(defer_ev->mail) : nullptr,
@@ -1453,15 +1550,15 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
         if (by_mail) defer_ev->by_mail = true;
         GR_LAUNCH_CHECK();
       } else {
+        // only the chunk totals: the scatter (SEG_SELF_SCAN) counts the tiles of its chunk and writes its row of seg_off
+        hipLaunchKernelGGL(chunk_total_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T), 0, stream, (int)P,
+                           num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_total);
         if (!short_rows)
           hipLaunchKernelGGL(chunk_max_kernel, dim3(1), dim3(1024), 0, stream, num_views * nchunk, g.chunk_total, g.chunk_max);
         GR_LAUNCH_CHECK();
         int rcs = exclusive_scan_i32(g.chunk_total, g.chunk_total + (int64_t)num_views * nchunk, nchunk, num_views, nchunk,
                                      g.scan_ws, g.totals, stream, nullptr, short_rows ? g.totals + num_views : nullptr);
         if (rcs != GR_OK) return rcs;
-        hipLaunchKernelGGL(seg_scan_kernel<false>, dim3((unsigned)(num_views * nchunk)), blk, 0, stream, num_views, tiles, nchunk,
-                           g.chunk_cnt, g.chunk_total + (int64_t)num_views * nchunk, g.totals, g.seg_off, (int32_t*)nullptr, 0);
-        GR_LAUNCH_CHECK();
       }
     }
     const bool short_rows = nchunk <= SCAN_SINGLE_ROW;
@@ -1633,14 +1730,16 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
   const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
   const unsigned int list_cap = spec ? (unsigned int)R : 0xffffffffu;
   if (R > 0 || (spec && P > 0)) {
-    // LDS: per-wave tile cursors + a staging block that holds a whole chunk's instances (chunks that do not fit write
-    // straight to global memory); sized for the largest chunk of this call, capped so that two workgroups share a CU
+    // LDS: per-wave 16-bit tile cursors + a staging block that holds a whole chunk's instances (chunks that do not fit write
+    // straight to global memory).  Many views: sized for SCATTER_WGS resident workgroups per CU (the chunks above that take
+    // the direct path), not for the largest chunk -- the scatter is latency-bound and wants the waves
     // few views: 1024 threads per workgroup (see the kernel) -- as long as their sixteen cursor rows leave room for the staging block
-    constexpr int WIDE_T = 1024;
     const bool wide = num_views <= 4 && (size_t)(WIDE_T / WAVE) * tiles * sizeof(unsigned int) <= 100 * 1024;
     const int scatter_threads = wide ? WIDE_T : BIN_T;
-    const size_t cur_bytes = (size_t)(scatter_threads / WAVE) * tiles * sizeof(unsigned int);
-    const int64_t cap_max = ((int64_t)(wide ? 156 : 78) * 1024 - (int64_t)cur_bytes) / 2;
+    const size_t cur_bytes = (size_t)(scatter_threads / WAVE) * ((tiles + 1) & ~1) * sizeof(unsigned short);
+    int64_t lds_budget = wide ? 156 * 1024 : 160 * 1024 / SCATTER_WGS - 512;
+    if (lds_budget < (int64_t)cur_bytes + 8 * 1024) lds_budget = 78 * 1024;  // (huge images: two workgroups, as before)
+    const int64_t cap_max = (lds_budget - (int64_t)cur_bytes) / 2;
     int64_t want = std::max<int64_t>(h_num_rendered[num_views], 0);
     if (spec) want = want > 0 ? want + 64 : cap_max;  // the hint is last frame's figure; a chunk that outgrows it writes straight
                                                       // to memory (a 25 % margin here cost a resident workgroup per CU: + 16 % scatter time)
@@ -1655,16 +1754,23 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
     rc = lds_atomics_lane_ordered(stream, &ordered);
     if (rc != GR_OK) return rc;
     const bool self_seg = spec && defer != nullptr && defer->self_seg;
+    const int seg_mode = self_seg ? SEG_SELF_RAW : bin_scans_self(nchunk, num_views) ? SEG_SELF_SCAN : SEG_READ;
     const SelfSeg self{g.chunk_total, g.totals, self_seg ? const_cast<int32_t*>(defer->mail) : nullptr, self_seg ? defer->seq : 0};
-    auto kern = self_seg ? (wide ? (ordered ? tile_scatter_kernel<true, WIDE_T, true> : tile_scatter_kernel<false, WIDE_T, true>)
-                                 : (ordered ? tile_scatter_kernel<true, BIN_T, true> : tile_scatter_kernel<false, BIN_T, true>))
-                : wide   ? (ordered ? tile_scatter_kernel<true, WIDE_T> : tile_scatter_kernel<false, WIDE_T>)
-                         : (ordered ? tile_scatter_kernel<true, BIN_T> : tile_scatter_kernel<false, BIN_T>);
+    auto pick = [&](bool lane_ordered) {
+#define GR_SCATTER(LO, S) (wide ? tile_scatter_kernel<LO, WIDE_T, S> : tile_scatter_kernel<LO, BIN_T, S>)
+      if (lane_ordered)
+        return seg_mode == SEG_SELF_RAW ? GR_SCATTER(true, SEG_SELF_RAW)
+               : seg_mode == SEG_SELF_SCAN ? GR_SCATTER(true, SEG_SELF_SCAN) : GR_SCATTER(true, SEG_READ);
+      return seg_mode == SEG_SELF_RAW ? GR_SCATTER(false, SEG_SELF_RAW)
+             : seg_mode == SEG_SELF_SCAN ? GR_SCATTER(false, SEG_SELF_SCAN) : GR_SCATTER(false, SEG_READ);
+#undef GR_SCATTER
+    };
+    auto kern = pick(ordered);
     int tile_bits = 0;
     while ((1 << tile_bits) < tiles) ++tile_bits;
     if (lds > 64 * 1024)
       GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 160 * 1024 - 512));  // (the SELF_SEG variants hold a few static words as well)
+                                 160 * 1024 - 512));  // (the SELF variants hold a few static words as well)
     {
       KernelTimer timer("raster_bin", stream);
       hipLaunchKernelGGL(kern, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(scatter_threads), lds, stream, (int)P, num_views, gx, gy,
@@ -1682,7 +1788,7 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
       if (rc != GR_OK) return rc;
       if (h_bad != 0 && ordered) {
         lds_order_demote();
-        auto kern_b = wide ? tile_scatter_kernel<false, WIDE_T> : tile_scatter_kernel<false, BIN_T>;
+        auto kern_b = pick(false);
         if (lds > 64 * 1024)
           GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_b), hipFuncAttributeMaxDynamicSharedMemorySize,
                                      160 * 1024 - 512));
