@@ -70,6 +70,12 @@ SIGNATURES.update({
     "gr_raster_backward_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
     "gr_raster_backward": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size, c_void,
                                    c_size, c_i64p, c_void, c_void, c_void, c_int] + [c_void] * 8 + [c_void, c_size, c_void]),
+    "gr_raster_render_aux": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
+                                     c_void, c_void, c_void, c_void, c_int, c_void]),
+    "gr_raster_backward_aux_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
+    "gr_raster_backward_aux": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size,
+                                       c_void, c_size, c_i64p, c_void, c_void, c_void, c_void, c_void, c_int] +
+                               [c_void] * 8 + [c_void, c_size, c_void]),
 })
 
 

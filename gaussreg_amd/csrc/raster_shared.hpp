@@ -153,8 +153,9 @@ __device__ __forceinline__ void sh_to_rgb(int deg, const float* pos, const float
 
 // geometry state: one 64-byte record per (view, Gaussian) so that the blend's per-instance gather
 // (ids arrive in depth order, i.e. random in memory) touches ONE 64-B sector instead of three lines:
-//   rec[0] = {px, py, sxx, syy (axis cull factors)}   rec[3] = {radius(int bits), depth, -, -}   rec[1] = {conic.x, conic.y, conic.z, opacity}
-//   rec[2] = {r, g, b, kc (cull factor)}          rec[3] = unused
+//   rec[0] = {px, py, sxx, syy (axis cull factors)}   rec[1] = {conic.x, conic.y, conic.z, opacity}
+//   rec[2] = {r, g, b, kc (cull factor)}              rec[3] = {radius (int bits), view-space depth z, 0, 0}
+// rec[3].y is what the depth map blends and what its backward differentiates (gr_raster_render_aux / _backward_aux).
 struct Geom {
   float4* rec;           // [V][P][4]
   uint32_t* dfield;      // [V*P] depth-sort field: rebased depth bits (see KEY_DEPTH_BITS), 0 = culled

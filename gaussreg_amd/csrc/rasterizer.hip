@@ -978,11 +978,26 @@ __device__ __forceinline__ float entry_alpha(float4 a, float cy, float op, f32x2
 // transmittance [V][H][W] (fp32) and n_contrib [V][H][W] (int32) = 1 + the index of the last blended entry in the tile's
 // concatenated list (0 = none) -- the state rasterizer_backward.hip starts from.  (No extra kernel argument: the
 // instances without KEEP keep their kernel-argument layout and compile to the instruction stream they had before.)
-template <bool FAST_EXP, bool KEEP = false>
+// AUX (gr_raster_render_aux): the walk also accumulates depth = sum w_i z_i (z_i: the view-space depth preprocess stored in
+// rec[3].y), with the red channel's operation (D = fma(z, w, D)), and writes it and alpha = 1 - T beside the colour.  z is
+// one more 4-byte plane s_z (entry e at byte 4 e, read with a ds_read_b32 only where the entry blends: the 16 lanes of a
+// cell read one address): 20 368 bytes of LDS per workgroup, still 8 workgroups per CU.  The output pointers travel in
+// BlendAux, which is empty without AUX: those instances keep their kernel arguments, their LDS and their instruction
+// stream.  With AUX the kept state (KEEP) goes to aux.state (final_T, then n_contrib) instead of behind the colour.
+template <bool AUX>
+struct BlendAux {};  // (without AUX: the kernel-argument segment keeps its size)
+template <>
+struct BlendAux<true> {
+  float* depth;  // [V][H][W]
+  float* alpha;  // [V][H][W]
+  float* state;  // final_T [V][H][W], n_contrib [V][H][W]; read only with KEEP
+};
+
+template <bool FAST_EXP, bool KEEP = false, bool AUX = false>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void blend_kernel(
     int P, int W, int H, int nchunk, const DevView* __restrict__ views, const uint32_t* __restrict__ seg_off,
     const int32_t* __restrict__ point_list, const float4* __restrict__ rec, float* __restrict__ out_color,
-    unsigned int list_cap) {
+    unsigned int list_cap, BlendAux<AUX> aux) {
   // One 40-byte record per entry, in three arrays, so that the walk reads an entry with two ds_read_b128 and one
   // ds_read_b64 (10 LDS-array cycles per wave) instead of ten ds_read_b32 (20):
   //   s_ga[e] = {px, py, conic x, conic z}   s_gb[e] = {conic y, opacity, power cutoff, red}   s_gc[e] = {green, blue}
@@ -990,6 +1005,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
   // share a bank only when their indices agree mod 16.)  Same 10 280 bytes as ten 257-entry planes: 8 workgroups per CU.
   __shared__ float4 s_ga[BLOCK + 1], s_gb[BLOCK + 1];
   __shared__ f32x2 s_gc[BLOCK + 1];
+  __shared__ float s_z[AUX ? BLOCK + 1 : 1];  // AUX only: view-space depth of the entry (without AUX: never touched, no LDS)
   __shared__ unsigned short s_list[NCELL][BLOCK + 2];                   // byte offsets (16 * entry) into s_ga / s_gb
   __shared__ int s_cnt[NCELL][BLOCK / WAVE];      // per (cell, loading wave) counts
   __shared__ int s_alldone[BLOCK / WAVE];
@@ -1019,8 +1035,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     s_ga[BLOCK] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     s_gb[BLOCK] = make_float4(0.0f, 0.0f, INFINITY, 0.0f);
     s_gc[BLOCK] = f32x2{0.0f, 0.0f};
+    if (AUX) s_z[BLOCK] = 0.0f;
   }
-  float T = 1.0f, C0 = 0.f;
+  float T = 1.0f, C0 = 0.f, Dz = 0.f;
   f32x2 C12 = {0.f, 0.f};
   // The tile's list = its segments of chunk 0, 1, 2, ... (depth order).  64 chunks are looked up at a time (one wave:
   // lane = chunk, two 4-byte loads give segment start and end); the batches of 256 entries are cut out of that window.
@@ -1091,6 +1108,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
       s_ga[tid] = make_float4(r0.x, r0.y, co.x, co.z);
       s_gb[tid] = make_float4(co.y, co.w, pc, col.x);
       s_gc[tid] = f32x2{col.y, col.z};
+      if (AUX) s_z[tid] = r[3].y;
     }
     float ex2[TILE / CELL], ey2[TILE / CELL];
     bool xin[TILE / CELL], yin[TILE / CELL];
@@ -1169,6 +1187,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
           const float w = alpha0 * T;
           C0 = fmaf(b0.w, w, C0);
           C12 = __builtin_elementwise_fma(lds_at(s_gc, o0 / 2), f32x2{w, w}, C12);
+          if (AUX) Dz = fmaf(lds_at(s_z, o0 / 4), w, Dz);
           T = test_T;
           if (KEEP) last = batch_base + (int)(o0 / 16) + 1;
         }
@@ -1181,6 +1200,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
           const float w = alpha1 * T;
           C0 = fmaf(b1.w, w, C0);
           C12 = __builtin_elementwise_fma(lds_at(s_gc, o1 / 2), f32x2{w, w}, C12);
+          if (AUX) Dz = fmaf(lds_at(s_z, o1 / 4), w, Dz);
           T = test_T;
           if (KEEP) last = batch_base + (int)(o1 / 16) + 1;
         }
@@ -1193,10 +1213,20 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     o[0] = fmaf(T, cam.bg[0], C0);
     o[(int64_t)H * W] = fmaf(T, cam.bg[1], C12.x);
     o[2 * (int64_t)H * W] = fmaf(T, cam.bg[2], C12.y);
+    if constexpr (AUX) {
+      const int64_t q = ((int64_t)v * H + pyi) * W + pxi;
+      aux.depth[q] = Dz;
+      aux.alpha[q] = 1.0f - T;
+    }
     if (KEEP) {
       const int64_t q = ((int64_t)v * H + pyi) * W + pxi, hw = (int64_t)gridDim.z * H * W;
-      out_color[3 * hw + q] = T;                                                      // final_T
-      reinterpret_cast<int32_t*>(out_color)[4 * hw + q] = last;                       // n_contrib
+      if constexpr (AUX) {
+        aux.state[q] = T;
+        reinterpret_cast<int32_t*>(aux.state)[hw + q] = last;
+      } else {
+        out_color[3 * hw + q] = T;                                                      // final_T
+        reinterpret_cast<int32_t*>(out_color)[4 * hw + q] = last;                       // n_contrib
+      }
     }
   }
 }
@@ -1704,7 +1734,8 @@ static int preprocess_collect(int64_t P, int num_views, int64_t* h_num_rendered,
 // refuse to run past the list (tile_scatter_kernel / blend_kernel list_cap).
 static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, const int64_t* h_num_rendered,
                        const void* geom, size_t geom_bytes, void* bin, size_t bin_bytes, float* out_color, int flags,
-                       int64_t spec_entries, hipStream_t stream, const Deferred* defer = nullptr, bool keep = false) {
+                       int64_t spec_entries, hipStream_t stream, const Deferred* defer = nullptr, bool keep = false,
+                       float* out_depth = nullptr, float* out_alpha = nullptr, float* aux_state = nullptr) {
   int rc = check_views(h_views, num_views);
   if (rc != GR_OK) return rc;
   GR_REQUIRE(out_color != nullptr && h_num_rendered != nullptr, "null argument");
@@ -1811,10 +1842,19 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
   const size_t blend_pad = (spec && (flags & GR_RASTER_SHARE)) ? 14000 : 0;
 #define GR_BLEND(FE, KEEP)                                                                                            \
   hipLaunchKernelGGL((blend_kernel<FE, KEEP>), dim3(gx, gy, num_views), dim3(BLOCK), blend_pad, stream, (int)P, W, H,      \
-                     blend_chunks, g.views, g.seg_off, point_list, g.rec, out_color, list_cap)
-  if (keep) { if (fast) GR_BLEND(true, true); else GR_BLEND(false, true); }
+                     blend_chunks, g.views, g.seg_off, point_list, g.rec, out_color, list_cap, BlendAux<false>{})
+#define GR_BLEND_AUX(FE, KEEP)                                                                                        \
+  hipLaunchKernelGGL((blend_kernel<FE, KEEP, true>), dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H,        \
+                     blend_chunks, g.views, g.seg_off, point_list, g.rec, out_color, list_cap,                           \
+                     BlendAux<true>{out_depth, out_alpha, aux_state})
+  if (out_depth != nullptr) {  // gr_raster_render_aux: depth and alpha beside the colour
+    if (keep) { if (fast) GR_BLEND_AUX(true, true); else GR_BLEND_AUX(false, true); }
+    else if (fast) GR_BLEND_AUX(true, false); else GR_BLEND_AUX(false, false);
+  }
+  else if (keep) { if (fast) GR_BLEND(true, true); else GR_BLEND(false, true); }
   else if (fast) GR_BLEND(true, false); else GR_BLEND(false, false);
 #undef GR_BLEND
+#undef GR_BLEND_AUX
   GR_LAUNCH_CHECK();
   frame_done();
   return GR_OK;
@@ -1832,6 +1872,15 @@ extern "C" int gr_raster_render_keep(int64_t P, const gr_raster_view* h_views, i
                                      void* bin, size_t bin_bytes, float* out_state, int flags, void* stream_) {
   return render_impl(P, h_views, num_views, h_num_rendered, geom, geom_bytes, bin, bin_bytes, out_state, flags, -1,
                      static_cast<hipStream_t>(stream_), nullptr, true);
+}
+
+extern "C" int gr_raster_render_aux(int64_t P, const gr_raster_view* h_views, int num_views,
+                                    const int64_t* h_num_rendered, const void* geom, size_t geom_bytes,
+                                    void* bin, size_t bin_bytes, float* out_color, float* out_depth, float* out_alpha,
+                                    float* out_state, int flags, void* stream_) {
+  GR_REQUIRE(out_depth != nullptr && out_alpha != nullptr, "out_depth / out_alpha is null");
+  return render_impl(P, h_views, num_views, h_num_rendered, geom, geom_bytes, bin, bin_bytes, out_color, flags, -1,
+                     static_cast<hipStream_t>(stream_), nullptr, out_state != nullptr, out_depth, out_alpha, out_state);
 }
 
 namespace gr {

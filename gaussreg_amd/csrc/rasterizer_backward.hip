@@ -14,6 +14,7 @@
 //                  fp32 (conic -> cov2D -> cov3D -> scale / quaternion, NDC mean -> mean, SH -> colour), accumulated over
 //                  the views in registers; every output is written once.
 #include <algorithm>
+#include <type_traits>
 
 #include "raster_shared.hpp"
 
@@ -21,6 +22,7 @@ namespace gr {
 namespace {
 
 constexpr int NF = 9;  // per (tile, entry): dL/d(px, py) (pixels), dL/dconic (a, b, c), dL/dopacity, dL/d(r, g, b)
+constexpr int NF_AUX = 10;  // gr_raster_backward_aux: + dL/dz (view-space depth), the "colour" of the depth map
 constexpr int NWAVE = BLOCK / WAVE;
 
 // wave-wide fp32 sum on the DPP shift network, fixed order (the inclusive-scan pattern; lane 63 holds the total)
@@ -80,16 +82,37 @@ __global__ __launch_bounds__(1024) void slot_block_scan_kernel(int nb, int32_t* 
 }
 
 // ------------------------------------------------------------------------------------ render backward
-template <bool FAST_EXP>
+// AUX (gr_raster_backward_aux): the depth map is a fourth colour channel whose per-entry colour is z (rec[3].y) and whose
+// background is 0, with its own accum / last recurrence; the alpha map adds +T_final / (1 - alpha) dL_dalpha_map to
+// dL_dalpha (the background term with -dL_dalpha_map for bg_dot).  Ten floats per slot, z as an eleventh s_e plane.
+// LDS: s_part and s_e grow by 5 120 bytes.  The slot index stays in a register (the thread that loads entry tid is the one
+// that stores its sums) and the strip mask is a byte: 53 008 bytes.  Three workgroups per CU, as without AUX (50 704, whose
+// layout is unchanged), need a margin below 160 KiB / 3: with 54 032 bytes (3 x = 162 096 < 163 840) only two were resident on
+// the device, measured as 1.53 x the kernel time.  (Presumably the LDS is allocated in blocks; their size was not measured.)
+// RenderBwdAux<false> is an empty struct: the instances without AUX keep their instruction stream; their kernel-argument
+// segment grows by four bytes (an empty C++ object still has a size) that no instruction reads.
+// Any of dL_dpix / aux.dL_ddepth / aux.dL_dalpha may be null with AUX (= zeros).
+template <bool AUX>
+struct RenderBwdAux {};
+template <>
+struct RenderBwdAux<true> {
+  const float* dL_ddepth;  // [V][H][W] or null
+  const float* dL_dalpha;  // [V][H][W] or null
+};
+
+template <bool FAST_EXP, bool AUX = false>
 __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
     int P, int W, int H, int nchunk, const DevView* __restrict__ views, const uint32_t* __restrict__ seg_off,
     const int32_t* __restrict__ point_list, const float4* __restrict__ rec, const uint32_t* __restrict__ rect_raw,
     const int32_t* __restrict__ slot_local, const int32_t* __restrict__ block_pre, int64_t slot_cap,
     const float* __restrict__ final_T, const int32_t* __restrict__ n_contrib, const float* __restrict__ dL_dpix,
-    float* __restrict__ slots) {
-  __shared__ float s_e[10][BLOCK];  // px, py, pc, conic a, b, c, opacity, r, g, b
-  __shared__ int64_t s_slot[BLOCK];
-  __shared__ unsigned int s_wmask[BLOCK];  // bit w: the entry can reach the pixel strip of wave w
+    float* __restrict__ slots, RenderBwdAux<AUX> aux) {
+  constexpr int NF = AUX ? NF_AUX : gr::NF;
+  using mask_t = typename std::conditional<AUX, unsigned char, unsigned int>::type;
+  __shared__ float s_e[AUX ? 11 : 10][BLOCK];  // px, py, pc, conic a, b, c, opacity, r, g, b (, z)
+  __shared__ int64_t s_slot[AUX ? 1 : BLOCK];  // AUX: my_slot instead; the one-element array is never touched and takes no LDS
+  int64_t my_slot = -1;
+  __shared__ mask_t s_wmask[BLOCK];  // bit w: the entry can reach the pixel strip of wave w
   __shared__ float s_part[NWAVE][BLOCK][NF];
   __shared__ int s_wpre[WAVE];
   __shared__ unsigned int s_woff[WAVE];
@@ -115,11 +138,16 @@ __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
   const float T_final = inside ? final_T[q] : 0.0f;
   const int last = inside ? n_contrib[q] : 0;
   float g[3] = {0.f, 0.f, 0.f};
-  if (inside) {
+  if (inside && (!AUX || dL_dpix != nullptr)) {
     const float* gp = dL_dpix + (int64_t)v * 3 * hw + (int64_t)pyi * W + pxi;
     g[0] = gp[0];
     g[1] = gp[hw];
     g[2] = gp[2 * hw];
+  }
+  float g_d = 0.f, g_a = 0.f, accum_d = 0.f, last_z = 0.f;  // AUX: dL/ddepth, dL/dalpha of the pixel; depth's recurrence
+  if constexpr (AUX) {
+    if (inside && aux.dL_ddepth != nullptr) g_d = aux.dL_ddepth[q];
+    if (inside && aux.dL_dalpha != nullptr) g_a = aux.dL_dalpha[q];
   }
   const DevView& cam = views[v];
   const float bg_dot = cam.bg[0] * g[0] + cam.bg[1] * g[1] + cam.bg[2] * g[2];
@@ -185,6 +213,7 @@ __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
         s_e[7][tid] = col.x;
         s_e[8][tid] = col.y;
         s_e[9][tid] = col.z;
+        if constexpr (AUX) s_e[10][tid] = r[3].y;
         // which wave strips (16 x 4 px) the entry can reach: the forward's cell test on the strip's box (a superset of
         // its four cells, so nothing the forward blended is skipped)
         const float ex = fmaxf(fmaxf(tx0 - r0.x, r0.x - (tx0 + (float)(TILE - 1))), 0.0f);
@@ -195,14 +224,14 @@ __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
           const float ey = fmaxf(fmaxf(ylo - r0.y, r0.y - (ylo + (float)(CELL - 1))), 0.0f);
           if (!(ex * ex + ey * ey > rc2) && !(ex * ex > hx2) && !(ey * ey > hy2)) m |= 1u << s;
         }
-        s_wmask[tid] = m;
+        s_wmask[tid] = (mask_t)m;
         int x0, y0, w, h;
         int64_t slot = -1;
         if (rect_decode(rect_raw[vbase + id], id, vbase, rec, gx, gy, x0, y0, w, h)) {
           const int64_t o = vbase + id;
           slot = (int64_t)slot_local[o] + block_pre[o >> 8] + (int64_t)((int)blockIdx.y - y0) * w + ((int)blockIdx.x - x0);
         }
-        s_slot[tid] = slot;
+        if (AUX) my_slot = slot; else s_slot[tid] = slot;
       }
       __syncthreads();
       // ---- back to front over the batch
@@ -236,9 +265,17 @@ __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
             dL_dalpha += (c - accum[ch]) * g[ch];
             val[6 + ch] = dchannel_dcolor * g[ch];
           }
+          if constexpr (AUX) {
+            const float z = s_e[10][j];
+            accum_d = last_alpha * last_z + (1.0f - last_alpha) * accum_d;
+            last_z = z;
+            dL_dalpha += (z - accum_d) * g_d;
+            val[9] = dchannel_dcolor * g_d;
+          }
           dL_dalpha *= T;
           last_alpha = alpha;
           dL_dalpha += (-T_final / (1.0f - alpha)) * bg_dot;
+          if constexpr (AUX) dL_dalpha += (T_final / (1.0f - alpha)) * g_a;
           const float dL_dG = op * dL_dalpha;  // straight-through 0.99 clamp
           const float gdx = G * dx, gdy = G * dy;
           val[0] = dL_dG * (-gdx * cx - gdy * cy);
@@ -261,7 +298,7 @@ __global__ __launch_bounds__(BLOCK) void render_backward_kernel(
       __syncthreads();
       // ---- the four waves' partial sums, in wave order -> the entry's slot
       if (tid < n) {
-        const int64_t slot = s_slot[tid];
+        const int64_t slot = AUX ? my_slot : s_slot[tid];
         if (slot >= 0 && slot < slot_cap) {  // (always: the host checked the slot layout against the instance count)
           float* dst = slots + NF * slot;
 #pragma unroll
@@ -329,13 +366,16 @@ struct BwdOut {
   float* cov3D;     // (P, 6)
 };
 
-template <bool HAS_SH, bool HAS_COV>
+// AUX: the slots hold NF_AUX floats; the tenth, dL/dz, reaches the mean through the third row of the view matrix
+// (z = view[2] p0 + view[6] p1 + view[10] p2 + view[14]).
+template <bool HAS_SH, bool HAS_COV, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     int P, int D, int M, int V, int W, int H, const DevView* __restrict__ views, const float* __restrict__ means3D,
     const float* __restrict__ shs, const float* __restrict__ scales, const float* __restrict__ rotations,
     const float* __restrict__ cov3D_precomp, const uint32_t* __restrict__ rect_raw, const float4* __restrict__ rec,
     const int32_t* __restrict__ slot_local, const int32_t* __restrict__ block_pre, int64_t slot_cap,
     const float* __restrict__ slots, BwdOut out) {
+  constexpr int NF = AUX ? NF_AUX : gr::NF;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
@@ -459,6 +499,10 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     for (int j = 0; j < 3; ++j)
       dmean[j] += Pm[j * 4 + 0] * dph0 + Pm[j * 4 + 1] * dph1 + Pm[j * 4 + 3] * dph3 +
                   Vm[j * 4 + 0] * dt[0] + Vm[j * 4 + 1] * dt[1] + Vm[j * 4 + 2] * dt[2];
+    if constexpr (AUX) {
+#pragma unroll
+      for (int j = 0; j < 3; ++j) dmean[j] += gs[9] * Vm[j * 4 + 2];
+    }
     dop += gs[5];
     // ---- colour
     if (HAS_SH) {
@@ -561,16 +605,16 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
 struct BwdScratch {
   int32_t* slot_local;  // [V * P]
   int32_t* block_pre;   // [ceil(V * P / 256)]
-  float* slots;         // [R][NF]
+  float* slots;         // [R][NF] (NF_AUX for gr_raster_backward_aux)
   size_t bytes;
 };
 
-BwdScratch carve_bwd(void* p, int64_t P, int V, int64_t R) {
+BwdScratch carve_bwd(void* p, int64_t P, int V, int64_t R, int nf = NF) {
   BwdScratch s;
   Carver c(p);
   s.slot_local = c.take<int32_t>(P * V);
   s.block_pre = c.take<int32_t>((P * V + 255) / 256 + 1);  // + the grand total
-  s.slots = c.take<float>(R * NF);
+  s.slots = c.take<float>(R * nf);
   s.bytes = c.used();
   return s;
 }
@@ -591,14 +635,21 @@ extern "C" size_t gr_raster_backward_bytes(int64_t P, int num_views, int width, 
   return carve_bwd(nullptr, P, num_views, total_rendered(h_num_rendered, num_views)).bytes;
 }
 
-extern "C" int gr_raster_backward(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
-                                  const float* opacities, const float* scales, const float* rotations,
-                                  const float* cov3D_precomp, const gr_raster_view* h_views, int num_views, const void* geom,
-                                  size_t geom_bytes, const void* bin, size_t bin_bytes, const int64_t* h_num_rendered,
-                                  const float* final_T, const int32_t* n_contrib, const float* dL_dcolor, int flags,
-                                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
-                                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
-                                  void* scratch, size_t scratch_bytes, void* stream_) {
+extern "C" size_t gr_raster_backward_aux_bytes(int64_t P, int num_views, int width, int height,
+                                               const int64_t* h_num_rendered) {
+  if (P < 0 || num_views < 1 || width <= 0 || height <= 0 || h_num_rendered == nullptr) return 0;
+  return carve_bwd(nullptr, P, num_views, total_rendered(h_num_rendered, num_views), NF_AUX).bytes;
+}
+
+// aux: gr_raster_backward_aux -- ten floats per slot, gradients of the depth and alpha maps; any map gradient may be null
+static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalpha, int64_t P, int M, const float* means3D,
+                         const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
+                         const float* rotations, const float* cov3D_precomp, const gr_raster_view* h_views, int num_views,
+                         const void* geom, size_t geom_bytes, const void* bin, size_t bin_bytes,
+                         const int64_t* h_num_rendered, const float* final_T, const int32_t* n_contrib,
+                         const float* dL_dcolor, int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs,
+                         float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                         void* scratch, size_t scratch_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   GR_REQUIRE(h_views != nullptr && num_views >= 1 && num_views <= MAX_VIEWS, "need 1 .. %d views", MAX_VIEWS);
   GR_REQUIRE(h_num_rendered != nullptr, "h_num_rendered is null");
@@ -622,8 +673,9 @@ extern "C" int gr_raster_backward(int64_t P, int M, const float* means3D, const 
   GR_REQUIRE(geom != nullptr && geom_bytes >= g.bytes, "geometry buffer missing or too small");
   const Bin bn = carve_bin(const_cast<void*>(bin), R, (int64_t)tiles * num_views);
   GR_REQUIRE(R == 0 || (bin != nullptr && bin_bytes >= bn.bytes), "binning buffer missing or too small");
-  GR_REQUIRE(R == 0 || (final_T != nullptr && n_contrib != nullptr && dL_dcolor != nullptr), "null per-pixel state");
-  const BwdScratch s = carve_bwd(scratch, P, num_views, R);
+  GR_REQUIRE(R == 0 || (final_T != nullptr && n_contrib != nullptr && (aux || dL_dcolor != nullptr)), "null per-pixel state");
+  const int nf = aux ? NF_AUX : NF;
+  const BwdScratch s = carve_bwd(scratch, P, num_views, R, nf);
   if (!scratch || scratch_bytes < s.bytes) {
     set_error("raster backward scratch too small: need %zu bytes, got %zu", s.bytes, scratch_bytes);
     return GR_ERR_WORKSPACE;
@@ -647,36 +699,67 @@ extern "C" int gr_raster_backward(int64_t P, int M, const float* means3D, const 
     const int32_t h_total = *h_tot;
     GR_REQUIRE(h_total == R, "raster backward: the tile rectangles hold %d instances, the forward binned %lld (geom / "
                "h_num_rendered not from the same forward call?)", h_total, (long long)R);
-    if (R > 0) GR_HIP(hipMemsetAsync(s.slots, 0, sizeof(float) * NF * R, stream));
+    if (R > 0) GR_HIP(hipMemsetAsync(s.slots, 0, sizeof(float) * nf * R, stream));
   }
   const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
   if (R > 0) {
     KernelTimer timer("raster_bwd_render", stream);
-    if (flags & GR_RASTER_FAST_EXP)
-      hipLaunchKernelGGL(render_backward_kernel<true>, dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H, nchunk,
-                         g.views, g.seg_off, bn.point_list, g.rec, g.rect_raw, s.slot_local, s.block_pre, R, final_T, n_contrib,
-                         dL_dcolor, s.slots);
-    else
-      hipLaunchKernelGGL(render_backward_kernel<false>, dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H, nchunk,
-                         g.views, g.seg_off, bn.point_list, g.rec, g.rect_raw, s.slot_local, s.block_pre, R, final_T, n_contrib,
-                         dL_dcolor, s.slots);
+#define GR_RBWD(FE, AUX, ...)                                                                                              \
+  hipLaunchKernelGGL((render_backward_kernel<FE, AUX>), dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H, nchunk, \
+                     g.views, g.seg_off, bn.point_list, g.rec, g.rect_raw, s.slot_local, s.block_pre, R, final_T, n_contrib,  \
+                     dL_dcolor, s.slots, RenderBwdAux<AUX>{__VA_ARGS__})
+    const bool fast = (flags & GR_RASTER_FAST_EXP) != 0;
+    if (aux) { if (fast) GR_RBWD(true, true, dL_ddepth, dL_dalpha); else GR_RBWD(false, true, dL_ddepth, dL_dalpha); }
+    else if (fast) GR_RBWD(true, false); else GR_RBWD(false, false);
+#undef GR_RBWD
     GR_LAUNCH_CHECK();
   }
   const BwdOut out{dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales, dL_drotations, dL_dcov3D};
   {
     KernelTimer timer("raster_bwd_preprocess", stream);
     const dim3 grd((unsigned)((P + 255) / 256)), blk(256);
-#define GR_PBWD(SH, COV)                                                                                                   \
-  hipLaunchKernelGGL((preprocess_backward_kernel<SH, COV>), grd, blk, 0, stream, (int)P, D, M, num_views, W, H, g.views,   \
-                     means3D, shs, scales, rotations, cov3D_precomp, g.rect_raw, g.rec, s.slot_local, s.block_pre, R,     \
-                     s.slots, out)
+#define GR_PBWD_(SH, COV, AUX)                                                                                            \
+  hipLaunchKernelGGL((preprocess_backward_kernel<SH, COV, AUX>), grd, blk, 0, stream, (int)P, D, M, num_views, W, H,      \
+                     g.views, means3D, shs, scales, rotations, cov3D_precomp, g.rect_raw, g.rec, s.slot_local,            \
+                     s.block_pre, R, s.slots, out)
+#define GR_PBWD(SH, COV) do { if (aux) GR_PBWD_(SH, COV, true); else GR_PBWD_(SH, COV, false); } while (0)
     if (shs && cov3D_precomp) GR_PBWD(true, true);
     else if (shs) GR_PBWD(true, false);
     else if (cov3D_precomp) GR_PBWD(false, true);
     else GR_PBWD(false, false);
 #undef GR_PBWD
+#undef GR_PBWD_
     GR_LAUNCH_CHECK();
   }
   (void)opacities;
   return GR_OK;
+}
+
+extern "C" int gr_raster_backward(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                                  const float* opacities, const float* scales, const float* rotations,
+                                  const float* cov3D_precomp, const gr_raster_view* h_views, int num_views, const void* geom,
+                                  size_t geom_bytes, const void* bin, size_t bin_bytes, const int64_t* h_num_rendered,
+                                  const float* final_T, const int32_t* n_contrib, const float* dL_dcolor, int flags,
+                                  float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
+                                  float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                  void* scratch, size_t scratch_bytes, void* stream_) {
+  return backward_impl(false, nullptr, nullptr, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
+                       cov3D_precomp, h_views, num_views, geom, geom_bytes, bin, bin_bytes, h_num_rendered, final_T, n_contrib,
+                       dL_dcolor, flags, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
+                       dL_drotations, dL_dcov3D, scratch, scratch_bytes, stream_);
+}
+
+extern "C" int gr_raster_backward_aux(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                                      const float* opacities, const float* scales, const float* rotations,
+                                      const float* cov3D_precomp, const gr_raster_view* h_views, int num_views,
+                                      const void* geom, size_t geom_bytes, const void* bin, size_t bin_bytes,
+                                      const int64_t* h_num_rendered, const float* final_T, const int32_t* n_contrib,
+                                      const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, int flags,
+                                      float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
+                                      float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                      void* scratch, size_t scratch_bytes, void* stream_) {
+  return backward_impl(true, dL_ddepth, dL_dalpha, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
+                       cov3D_precomp, h_views, num_views, geom, geom_bytes, bin, bin_bytes, h_num_rendered, final_T, n_contrib,
+                       dL_dcolor, flags, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
+                       dL_drotations, dL_dcov3D, scratch, scratch_bytes, stream_);
 }

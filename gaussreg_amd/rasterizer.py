@@ -8,6 +8,7 @@ upstream one (graphdeco-inria/diff-gaussian-rasterization, diff_gaussian_rasteri
     GaussianRasterizer(raster_settings).forward(means3D, means2D, opacities, shs=None,
         colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None) -> (color, radii)
     GaussianRasterizer.markVisible(positions) -> BoolTensor
+    GaussianRasterizer(raster_settings, render_depth=True).forward(...) -> (color, radii, depth, alpha)   (extension)
 
 plus `rasterize_views(...)`: many cameras over one Gaussian set in one launch sequence (the
 throughput path: per-Gaussian inputs are read once per batch).
@@ -280,13 +281,94 @@ class _RasterizeViews(torch.autograd.Function):
         return None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov
 
 
+def _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, keep):
+    """gr_raster_preprocess + gr_raster_render_aux, serial, on the caller's stream.  Inputs: fp32, contiguous, on the device.
+    Returns (color, radii, depth, alpha, num_rendered array, M, geom, bin, state); state (final_T, n_contrib) only with
+    `keep`.  Every map is a tensor of its own."""
+    dev = m.device
+    L = _lib.lib()
+    V, views, H, W = vb.count, vb.array, vb.height, vb.width
+    P = m.shape[0]
+    M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
+    st = _lib.stream_ptr(dev)
+    nr = (ctypes.c_int64 * (V + 1))()
+    color = torch.empty((3, H, W) if one else (V, 3, H, W), dtype=torch.float32, device=dev)
+    depth = torch.empty((1, H, W) if one else (V, 1, H, W), dtype=torch.float32, device=dev)
+    alpha = torch.empty_like(depth)
+    state = torch.empty(2 * V * H * W, dtype=torch.float32, device=dev) if keep else None
+    radii = torch.empty((P,) if one else (V, P), dtype=torch.int32, device=dev)
+    gbytes = L.gr_raster_geom_bytes(P, V, W, H) + 256
+    geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
+    ptrs = (_lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov))
+    _lib.check(L.gr_raster_preprocess(P, M, *ptrs, views, V, _lib.ptr(radii), _lib.ptr(geom), gbytes, nr, st))
+    total = sum(int(nr[v]) for v in range(V))
+    binb = torch.empty(L.gr_raster_bin_bytes(total, W, H, V) + 256, dtype=torch.uint8, device=dev)
+    _lib.check(L.gr_raster_render_aux(P, views, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel(),
+                                      _lib.ptr(color), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(state), flags, st))
+    return color, radii, depth, alpha, nr, M, geom, binb, state
+
+
+class _RasterizeViewsAux(torch.autograd.Function):
+    """_RasterizeViews with the depth and alpha maps: forward gr_raster_preprocess + gr_raster_render_aux, backward
+    gr_raster_backward_aux.  Output gradients autograd did not produce are passed as null pointers."""
+
+    @staticmethod
+    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov):
+        color, radii, depth, alpha, nr, M, geom, binb, state = _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, True)
+        ctx.vb, ctx.flags, ctx.M, ctx.nr = vb, flags, M, nr
+        ctx.geom, ctx.binb, ctx.state = geom, binb, state
+        ctx.m2d = None if m2d is None else (m2d.shape, m2d.dtype, m2d.device)
+        ctx.save_for_backward(m, op, sh, cp, sc, rot, cov)
+        ctx.mark_non_differentiable(radii)
+        box.extend(int(nr[v]) for v in range(vb.count))
+        return color, radii, depth, alpha
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
+        m, op, sh, cp, sc, rot, cov = ctx.saved_tensors
+        dev = m.device
+        L = _lib.lib()
+        vb = ctx.vb
+        V, H, W = vb.count, vb.height, vb.width
+        P = m.shape[0]
+        need = ctx.needs_input_grad
+
+        def grad(t):
+            return None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
+        gc, gd, ga = grad(grad_color), grad(grad_depth), grad(grad_alpha)
+
+        def out(t, i):
+            return torch.empty_like(t) if (t is not None and need[i]) else None
+        dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
+                                             out(cov, 11))
+        dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
+        hw = H * W
+        final_T = ctx.state[:V * hw]
+        n_contrib = ctx.state[V * hw:]
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            sbytes = L.gr_raster_backward_aux_bytes(P, V, W, H, ctx.nr) + 256
+            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+            _lib.check(L.gr_raster_backward_aux(
+                P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov),
+                vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(), ctx.nr,
+                _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags, _lib.ptr(dm),
+                _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov),
+                _lib.ptr(scratch), scratch.numel(), st))
+        if dm2 is not None:
+            shape, dtype, device = ctx.m2d
+            dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
+        return None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov
+
+
 def _wants_grad(*ts):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
 
 def rasterize_views(settings, means3D, opacities, shs=None,
                     colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, fast_exp=None, _one=False,
-                    static_scene=False, *, means2D=None):
+                    static_scene=False, *, means2D=None, render_depth=False):
     """Render the same Gaussians from len(settings) cameras (`settings`: a sequence of
     GaussianRasterizationSettings, or a prebuilt ViewBatch).
 
@@ -303,7 +385,13 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     Autograd: when grad mode is on and any input requires grad, the call is differentiable (see the module docstring);
     it then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
     `means2D` (keyword only, extension): a (V, P, 3) tensor (upstream's (P, 3) screen-space means for one camera) whose
-    .grad receives dL/d(NDC position) per view; its values are not read."""
+    .grad receives dL/d(NDC position) per view; its values are not read.
+
+    `render_depth=True` (keyword only): returns (color, radii, num_rendered, depth, alpha) with depth and alpha of shape
+    (V,1,H,W) fp32: depth = sum_i w_i z_i over the entries the colour blend blends (w_i its weights, z_i the view-space
+    depth; the background adds nothing), alpha = 1 - final transmittance.  color and radii are bit-identical to the
+    call without it.  Differentiable like the colour.  The call runs serially on the caller's stream with and without
+    grad: `static_scene` is ignored on this path."""
     dev = means3D.device if means3D.is_cuda else _lib.require_gpu()
     L = _lib.lib()
     n_pts = int(means3D.shape[0])
@@ -332,7 +420,7 @@ def rasterize_views(settings, means3D, opacities, shs=None,
             torch.cuda.set_device(dev)
         box = []
         try:
-            color, radii = _RasterizeViews.apply(
+            res = (_RasterizeViewsAux if render_depth else _RasterizeViews).apply(
                 vb, _flags(fast_exp), _one and vb.count == 1, box, _dev_f32_grad(means3D, dev), means2D,
                 _dev_f32_grad(opacities, dev), _dev_f32_grad(shs, dev) if given(shs) else None,
                 _dev_f32_grad(colors_precomp, dev) if given(colors_precomp) else None,
@@ -341,7 +429,9 @@ def rasterize_views(settings, means3D, opacities, shs=None,
         finally:
             if home != dev.index:
                 torch.cuda.set_device(home)
-        return color, radii, box
+        if render_depth:
+            return res[0], res[1], box, res[2], res[3]
+        return res[0], res[1], box
     V, views, H, W = vb.count, vb.array, vb.height, vb.width
     m = _dev_f32(means3D, dev, "means3D")
     if m.dim() != 2 or m.shape[1] != 3:
@@ -353,6 +443,17 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     sc = _dev_f32(scales, dev, "scales") if has_sr else None
     rot = _dev_f32(rotations, dev, "rotations") if has_sr else None
     cov = _dev_f32(cov3D_precomp, dev, "cov3D_precomp") if has_cov else None
+    if render_depth:
+        home = torch.cuda.current_device()
+        if home != dev.index:
+            torch.cuda.set_device(dev)
+        try:
+            color, radii, depth, alpha, nr = _render_aux(vb, _flags(fast_exp), _one and V == 1, m, op, sh, cp, sc, rot, cov,
+                                                         False)[:5]
+        finally:
+            if home != dev.index:
+                torch.cuda.set_device(home)
+        return color, radii, [int(nr[v]) for v in range(V)], depth, alpha
     M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
     nr = (ctypes.c_int64 * (V + 1))()
     pipe = _frame_pipe(dev, static_scene)
@@ -442,19 +543,29 @@ def rasterize_views(settings, means3D, opacities, shs=None,
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
-                        raster_settings, fast_exp=None, static_scene=False):
-    """`raster_settings`: GaussianRasterizationSettings, or a one-camera ViewBatch built from it (marshalled once)."""
+                        raster_settings, fast_exp=None, static_scene=False, render_depth=False):
+    """`raster_settings`: GaussianRasterizationSettings, or a one-camera ViewBatch built from it (marshalled once).
+    `render_depth=True`: returns (color, radii, depth, alpha), depth and alpha of shape (1, H, W) (see rasterize_views)."""
     vb = raster_settings if isinstance(raster_settings, ViewBatch) else [raster_settings]
+    m2d = means2D if isinstance(means2D, torch.Tensor) and means2D.requires_grad else None
+    if render_depth:
+        color, radii, _, depth, alpha = rasterize_views(vb, means3D, opacities, sh, colors_precomp, scales, rotations,
+                                                        cov3Ds_precomp, fast_exp=fast_exp, _one=True, means2D=m2d,
+                                                        render_depth=True)
+        return color, radii, depth, alpha
     color, radii, _ = rasterize_views(vb, means3D, opacities, sh, colors_precomp, scales, rotations, cov3Ds_precomp,
-                                      fast_exp=fast_exp, _one=True, static_scene=static_scene,
-                                      means2D=means2D if isinstance(means2D, torch.Tensor) and means2D.requires_grad else None)
+                                      fast_exp=fast_exp, _one=True, static_scene=static_scene, means2D=m2d)
     return color, radii
 
 
 class GaussianRasterizer(torch.nn.Module):
-    def __init__(self, raster_settings: GaussianRasterizationSettings, fast_exp=None, static_scene=False):
-        """`fast_exp`, `static_scene` (extensions, upstream has no such arguments): see rasterize_views."""
+    def __init__(self, raster_settings: GaussianRasterizationSettings, fast_exp=None, static_scene=False,
+                 render_depth=False):
+        """`fast_exp`, `static_scene` (extensions, upstream has no such arguments): see rasterize_views.
+        `render_depth=True`: forward returns (color, radii, depth, alpha) with depth and alpha of shape (1, H, W), the
+        order and shapes of the common depth forks of upstream; `static_scene` is then ignored."""
         super().__init__()
+        self.render_depth = render_depth
         self.raster_settings = raster_settings
         self.fast_exp = fast_exp
         self.static_scene = static_scene
@@ -500,4 +611,5 @@ class GaussianRasterizer(torch.nn.Module):
                 ((scales is not None or rotations is not None) and cov3D_precomp is not None):
             raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
         return rasterize_gaussians(means3D, means2D, shs, colors_precomp, opacities, scales, rotations,
-                                   cov3D_precomp, self._views(), fast_exp=self.fast_exp, static_scene=self.static_scene)
+                                   cov3D_precomp, self._views(), fast_exp=self.fast_exp, static_scene=self.static_scene,
+                                   render_depth=self.render_depth)

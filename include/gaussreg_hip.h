@@ -271,6 +271,36 @@ int gr_raster_backward(int64_t P, int M, const float* means3D, const float* shs,
                        const float* dL_dcolor, int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs,
                        float* dL_dcolors, float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                        void* scratch, size_t scratch_bytes, void* stream);
+/* Depth and accumulated-alpha maps (INTEGRATION.md "Depth and alpha").  Per pixel, over the entries the colour blend
+ * blends, in its order, with its weights w_i = alpha_i T_i (same skip and stop rules; GR_RASTER_FAST_EXP applies to the
+ * weights as it does for colour):
+ *   depth = sum_i w_i z_i   z_i = the fp32 view-space depth of the Gaussian (third row of viewmatrix applied to the mean),
+ *                           accumulated as D = fmaf(z_i, w_i, D) from 0 -- the red channel's operation; no background term
+ *   alpha = 1.0f - T        T = the pixel's final transmittance (final_T of gr_raster_render_keep)
+ * A pixel no Gaussian reaches has depth = 0, alpha = 0.
+ * gr_raster_render_aux: gr_raster_render_ex that also writes out_depth and out_alpha, (num_views, H, W) fp32 each, both
+ * required.  out_color is bit-identical to gr_raster_render_ex's.  out_state: NULL, or (the autograd forward) final_T
+ * (num_views, H, W) fp32 followed by n_contrib (num_views, H, W) int32, the two planes gr_raster_render_keep appends to its
+ * image.  Call it after gr_raster_preprocess (no speculation); keep geom and bin for the backward.
+ * gr_raster_backward_aux: gr_raster_backward plus the gradients of the two maps, dL_ddepth and dL_dalpha (num_views, H, W).
+ * Each of dL_dcolor, dL_ddepth, dL_dalpha may be NULL and then counts as zeros.  Same contract, checks and error codes as
+ * gr_raster_backward, and in addition:
+ *   - depth is a fourth colour channel whose per-Gaussian colour is z_i and whose background is 0; dL/dz_i = sum over
+ *     pixels of w_i dL_ddepth reaches dL_dmeans3D through the third row of viewmatrix
+ *   - alpha adds +final_T / (1 - alpha_i) dL_dalpha to dL/dalpha_i of every blended entry
+ * scratch: gr_raster_backward_aux_bytes(...) bytes (ten floats per instance instead of gr_raster_backward's nine). */
+int gr_raster_render_aux(int64_t P, const gr_raster_view* h_views, int num_views, const int64_t* h_num_rendered,
+                         const void* geom, size_t geom_bytes, void* bin, size_t bin_bytes, float* out_color,
+                         float* out_depth, float* out_alpha, float* out_state, int flags, void* stream);
+size_t gr_raster_backward_aux_bytes(int64_t P, int num_views, int width, int height, const int64_t* h_num_rendered);
+int gr_raster_backward_aux(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                           const gr_raster_view* h_views, int num_views, const void* geom, size_t geom_bytes,
+                           const void* bin, size_t bin_bytes, const int64_t* h_num_rendered, const float* final_T,
+                           const int32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                           int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
+                           float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
+                           size_t scratch_bytes, void* stream);
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (markVisible). */
 int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewmatrix,
                            uint8_t* present, void* stream);
