@@ -858,9 +858,9 @@ extern "C" int gr_rpe_attention(const float* embed, const float* u, const float*
 #define GR_RPA(H, CV)                                                                                            \
   do {                                                                                                           \
     auto kern = gr::rpe_attention_kernel<H, CV>;                                                                 \
-    if (lds > 64 * 1024)                                                                                         \
+    if (lds > 64 * 1024) /* what this launch needs: the kernel's static LDS counts against the CU's 160 KB too */ \
       GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                 160 * 1024));                                                                   \
+                                 (int)lds));                                                                     \
     hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(256), lds, stream, embed, u, add, q, k, v, attention_factors, \
                        key_weights, key_masks, (int)n, (int)m, inv_sqrt_ch, out_scores, out_hidden);             \
   } while (0)

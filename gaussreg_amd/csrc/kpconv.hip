@@ -474,6 +474,37 @@ extern "C" size_t gr_kpconv_workspace_bytes(int64_t n, int64_t m, int64_t k, int
          align_up((size_t)n + 1, 256) + 1024;
 }
 
+// The variant choice of gr_kpconv_forward, host only (include/gaussreg_hip.h lists the codes): gr_kpconv_forward dispatches
+// on this value and on nothing else, so what the query reports is what runs.
+extern "C" int gr_kpconv_plan(int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout, int64_t k, int operands_aligned) {
+  if (n < 0 || m <= 0 || h < 0 || cin < 1 || cout < 1 || k < 1 || k > KP_MAX) return -1;
+  int gather;
+  const bool mfma = n > 0 && h <= 4 * KP_STEPS && (cin == 16 || cin == 32 || cin == 64 || cin == 128 || cin == 256);
+  if (mfma) {
+    gather = cin == 16 ? GR_KP_GATHER_MFMA_1 : cin == 32 ? GR_KP_GATHER_MFMA_2 : cin == 64 ? GR_KP_GATHER_MFMA_4
+           : cin == 128 ? GR_KP_GATHER_MFMA_8 : GR_KP_GATHER_MFMA_16;
+  } else {
+    const int t = cin <= 64 ? 64 : cin <= 128 ? 128 : 256;
+    gather = t == 64 ? GR_KP_GATHER_T64 : t == 128 ? GR_KP_GATHER_T128 : GR_KP_GATHER_T256;
+    if (cin > t) gather |= GR_KP_GATHER_FLUSH;
+    if (h > KP_HMAX) gather |= GR_KP_GATHER_CHUNKED;
+  }
+  const int64_t kd = k * cin;
+  const bool aligned = kd % BK == 0 && cout % 4 == 0 && cout >= 4 && operands_aligned != 0;
+  int product;
+  if (m >= BT && cout > 64) {
+    const int64_t blocks128 = ((cout + BT - 1) / BT) * ((m + BT - 1) / BT);
+    // three or more 128-row workgroups per CU: the big tile's operand reuse wins
+    product = (blocks128 >= 768 ? GR_KP_PRODUCT_128X128 : GR_KP_PRODUCT_64X128) | (aligned ? GR_KP_PRODUCT_ALIGNED : 0);
+  } else if (m >= BT && cout > 16) {
+    // narrow outputs (the 32- and 64-channel stages): 128 x 64 tiles, same double-buffered pipeline
+    product = GR_KP_PRODUCT_128X64 | (aligned ? GR_KP_PRODUCT_ALIGNED : 0);
+  } else {
+    product = GR_KP_PRODUCT_SMALL;
+  }
+  return gather | product << 8;
+}
+
 extern "C" int gr_kpconv_forward(const float* s_feats, const float* q_points, const float* s_points,
                                  const int64_t* neighbor_indices, int64_t n, int64_t m, int64_t h, int64_t cin,
                                  int64_t cout, const float* kernel_points, int64_t k, const float* weights,
@@ -484,7 +515,10 @@ extern "C" int gr_kpconv_forward(const float* s_feats, const float* q_points, co
   GR_REQUIRE(k <= KP_MAX, "kernel_size must be <= %d", KP_MAX);
   GR_REQUIRE(m * k * cin < (1ll << 40) && n < (1ll << 31) && m < (1ll << 31), "sizes too large");
   if (m == 0) return GR_OK;
-  GR_REQUIRE(s_feats && q_points && s_points && neighbor_indices && kernel_points && weights && out, "null argument");
+  // no support points (every neighbour is the shadow point) or no neighbour columns: nothing of s_feats / s_points /
+  // neighbor_indices is read -- an empty tensor has no address -- and the output is the bias (kpconv.py:103-120 on zeros)
+  GR_REQUIRE((n == 0 || (s_feats && s_points)) && (h == 0 || neighbor_indices) && q_points && kernel_points && weights && out,
+             "null argument");
   if (!ws || ws_bytes < gr_kpconv_workspace_bytes(n, m, k, cin)) {
     set_error("kpconv workspace too small");
     return GR_ERR_WORKSPACE;
@@ -495,54 +529,52 @@ extern "C" int gr_kpconv_forward(const float* s_feats, const float* q_points, co
   float* num = reinterpret_cast<float*>(p);
   p += align_up((size_t)m * sizeof(float), 256);
   uint8_t* flag = reinterpret_cast<uint8_t*>(p);
+  const int plan = gr_kpconv_plan(n, m, h, cin, cout, k,
+                                  ((reinterpret_cast<uintptr_t>(WF) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0);
+  GR_REQUIRE(plan >= 0, "bad sizes");
   KernelTimer timer("kpconv", stream);
   if (n > 0)
     hipLaunchKernelGGL(rowflag_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, s_feats, (int)n, (int)cin, flag);
   const size_t kp_lds = (size_t)std::min<int64_t>(h, KP_HMAX) * (KP_MAX + 2) * sizeof(float);
-  const bool mfma = n > 0 && h <= 4 * KP_STEPS && (cin == 16 || cin == 32 || cin == 64 || cin == 128 || cin == 256);
-  if (mfma) {
-    const dim3 grid((unsigned)((m + 3) / 4)), blk(256);
 #define GR_KP_MFMA(NT)                                                                                                       \
-  hipLaunchKernelGGL((kp_gather_mfma_kernel<NT>), grid, blk, 0, stream, s_feats, q_points, s_points, neighbor_indices, (int)n, \
-                     (int)m, (int)h, (int)k, kernel_points, sigma, inf, flag, WF, num)
-    if (cin == 16) GR_KP_MFMA(1);
-    else if (cin == 32) GR_KP_MFMA(2);
-    else if (cin == 64) GR_KP_MFMA(4);
-    else if (cin == 128) GR_KP_MFMA(8);
-    else GR_KP_MFMA(16);
-#undef GR_KP_MFMA
-  } else if (cin <= 64)
-    hipLaunchKernelGGL((kp_gather_kernel<64>), dim3((unsigned)m), dim3(64), kp_lds, stream, s_feats, q_points, s_points,
-                       neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num);
-  else if (cin <= 128)
-    hipLaunchKernelGGL((kp_gather_kernel<128>), dim3((unsigned)m), dim3(128), kp_lds, stream, s_feats, q_points, s_points,
-                       neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num);
-  else
-    hipLaunchKernelGGL((kp_gather_kernel<256>), dim3((unsigned)m), dim3(256), kp_lds, stream, s_feats, q_points, s_points,
-                       neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num);
-  const int kd = (int)(k * cin);
-  const bool aligned = kd % BK == 0 && cout % 4 == 0 && cout >= 4 &&
-                       ((reinterpret_cast<uintptr_t>(WF) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0;
-  if (m >= BT && cout > 64) {
-    const int64_t blocks128 = ((cout + BT - 1) / BT) * ((m + BT - 1) / BT);
-    if (blocks128 >= 768) {  // three or more 128-row workgroups per CU: the big tile's operand reuse wins
-      const dim3 grid((unsigned)((cout + BT - 1) / BT), (unsigned)((m + BT - 1) / BT));
-      if (aligned) hipLaunchKernelGGL((gemm_nn_big_kernel<128, 128, true>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-      else hipLaunchKernelGGL((gemm_nn_big_kernel<128, 128>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-    } else {
-      const dim3 grid((unsigned)((cout + BT - 1) / BT), (unsigned)((m + 63) / 64));
-      if (aligned) hipLaunchKernelGGL((gemm_nn_big_kernel<64, 128, true>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-      else hipLaunchKernelGGL((gemm_nn_big_kernel<64, 128>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-    }
-  } else if (m >= BT && cout > 16) {
-    // narrow outputs (the 32- and 64-channel stages): 128 x 64 tiles, same double-buffered pipeline
-    const dim3 grid((unsigned)((cout + 63) / 64), (unsigned)((m + BT - 1) / BT));
-    if (aligned) hipLaunchKernelGGL((gemm_nn_big_kernel<128, 64, true>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-    else hipLaunchKernelGGL((gemm_nn_big_kernel<128, 64>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
-  } else {
-    const dim3 grid((unsigned)((cout + GT - 1) / GT), (unsigned)((m + GT - 1) / GT));
-    hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
+  hipLaunchKernelGGL((kp_gather_mfma_kernel<NT>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, s_feats, q_points,    \
+                     s_points, neighbor_indices, (int)n, (int)m, (int)h, (int)k, kernel_points, sigma, inf, flag, WF, num)
+#define GR_KP_GENERIC(T)                                                                                                   \
+  hipLaunchKernelGGL((kp_gather_kernel<T>), dim3((unsigned)m), dim3(T), kp_lds, stream, s_feats, q_points, s_points,       \
+                     neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num)
+  switch (plan & GR_KP_GATHER_KERNEL_MASK) {
+    case GR_KP_GATHER_MFMA_1: GR_KP_MFMA(1); break;
+    case GR_KP_GATHER_MFMA_2: GR_KP_MFMA(2); break;
+    case GR_KP_GATHER_MFMA_4: GR_KP_MFMA(4); break;
+    case GR_KP_GATHER_MFMA_8: GR_KP_MFMA(8); break;
+    case GR_KP_GATHER_MFMA_16: GR_KP_MFMA(16); break;
+    case GR_KP_GATHER_T64: GR_KP_GENERIC(64); break;
+    case GR_KP_GATHER_T128: GR_KP_GENERIC(128); break;
+    default: GR_KP_GENERIC(256); break;
   }
+#undef GR_KP_GENERIC
+#undef GR_KP_MFMA
+  const int kd = (int)(k * cin);
+  const int product = plan >> 8;
+  const bool aligned = (product & GR_KP_PRODUCT_ALIGNED) != 0;
+#define GR_KP_BIG(BM_, BN_)                                                                                                 \
+  do {                                                                                                                      \
+    const dim3 grid((unsigned)((cout + BN_ - 1) / BN_), (unsigned)((m + BM_ - 1) / BM_));                                   \
+    if (aligned) hipLaunchKernelGGL((gemm_nn_big_kernel<BM_, BN_, true>), grid, dim3(256), 0, stream, WF, weights, (int)m,  \
+                                    (int)cout, kd, num, bias, out);                                                         \
+    else hipLaunchKernelGGL((gemm_nn_big_kernel<BM_, BN_>), grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, \
+                            num, bias, out);                                                                                \
+  } while (0)
+  switch (product & ~GR_KP_PRODUCT_ALIGNED) {
+    case GR_KP_PRODUCT_128X128: GR_KP_BIG(128, 128); break;
+    case GR_KP_PRODUCT_64X128: GR_KP_BIG(64, 128); break;
+    case GR_KP_PRODUCT_128X64: GR_KP_BIG(128, 64); break;
+    default: {
+      const dim3 grid((unsigned)((cout + GT - 1) / GT), (unsigned)((m + GT - 1) / GT));
+      hipLaunchKernelGGL(gemm_nn_kernel, grid, dim3(256), 0, stream, WF, weights, (int)m, (int)cout, kd, num, bias, out);
+    }
+  }
+#undef GR_KP_BIG
   GR_LAUNCH_CHECK();
   return GR_OK;
 }
@@ -604,7 +636,7 @@ extern "C" int gr_neighbor_pool(const float* x, int64_t n, int64_t c, const int6
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   GR_REQUIRE(n >= 0 && c >= 1 && m >= 0 && h >= 1 && (mode == 0 || mode == 1), "bad arguments");
   if (m == 0) return GR_OK;
-  GR_REQUIRE(x && neighbor_indices && out, "null argument");
+  GR_REQUIRE((n == 0 || x) && neighbor_indices && out, "null argument");  // n == 0: every index is the shadow row, x is not read
   if (c % 4 == 0 && n > 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0)
     hipLaunchKernelGGL(pool4_kernel, dim3((unsigned)((m * (c / 4) + 255) / 256)), dim3(256), 0, stream,
                        reinterpret_cast<const float4*>(x), (int)n, (int)(c / 4), neighbor_indices, (int)m, (int)h, mode,

@@ -48,13 +48,6 @@ class RPEMultiHeadAttention(nn.Module):
         B, N, C = input_q.shape
         M = input_k.shape[1]
         H, ch = self.num_heads, self.d_model_per_head
-        q2 = self.proj_q(input_q).contiguous()                                   # (B,N,C), heads side by side
-        k2 = self.proj_k(input_k).contiguous()
-        v2 = self.proj_v(input_v).contiguous()
-        wp = self.proj_p.weight.view(H, ch, C)                                  # rows h*ch..: head h
-        qh = q2.view(B, N, H, ch)
-        u = torch.einsum('bnhc,hcj->bnhj', qh, wp).contiguous()                 # (B,N,H,C)
-        add = torch.einsum('bnhc,hc->bnh', qh, self.proj_p.bias.view(H, ch)).contiguous()
         emb = embed_qk.to(torch.float32).contiguous()
         scores = torch.empty((B, H, N, M), dtype=torch.float32, device=dev)
         hidden = torch.empty((B, N, C), dtype=torch.float32, device=dev)
@@ -64,14 +57,30 @@ class RPEMultiHeadAttention(nn.Module):
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
             for b in range(B):
-                _lib.check(L.gr_rpe_attention(_lib.ptr(emb[b]), _lib.ptr(u[b]), _lib.ptr(add[b]), _lib.ptr(q2[b]),
-                                              _lib.ptr(k2[b]), _lib.ptr(v2[b]), _lib.ptr(None if fac is None else fac[b]),
+                q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
+                _lib.check(L.gr_rpe_attention(_lib.ptr(emb[b]), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2),
+                                              _lib.ptr(k2), _lib.ptr(v2), _lib.ptr(None if fac is None else fac[b]),
                                               _lib.ptr(None if kw is None else kw[b]), _lib.ptr(None if km is None else km[b]),
                                               N, M, C, H, _lib.ptr(scores[b]), _lib.ptr(hidden[b]), st))
         if not isinstance(self.dropout, nn.Identity):
             scores = self.dropout(scores)  # inference: identity (the reference applies dropout to the scores before @ v)
         return hidden, scores
 
+
+    def _project(self, xq, xk, xv):
+        """The torch side of ONE batch element, (n,C) / (m,C) / (m,C) matrices: the three input projections (heads side by
+        side), u = W_p[h]^T q[h] (n,H,C) and add = q[h] . b_p[h] (n,H).  Per element on purpose: the GEMM a BLAS call runs
+        -- and with it the last bit of every product -- follows the operand shapes, nn.Linear included, so projections taken
+        over a whole (padded) batch differ from the single call's.  Every element goes through the same calls with the shapes
+        it has alone: a batched, a padded and a single call then return the same bits."""
+        H, ch, C = self.num_heads, self.d_model_per_head, self.d_model
+        q2 = self.proj_q(xq.contiguous()).contiguous()
+        k2 = self.proj_k(xk.contiguous()).contiguous()
+        v2 = self.proj_v(xv.contiguous()).contiguous()
+        qh = q2.view(-1, H, ch)
+        u = torch.einsum('nhc,hcj->nhj', qh, self.proj_p.weight.view(H, ch, C)).contiguous()   # rows h*ch..: head h
+        add = torch.einsum('nhc,hc->nh', qh, self.proj_p.bias.view(H, ch)).contiguous()
+        return q2, k2, v2, u, add
 
     @torch.no_grad()
     def _forward_ragged(self, input_q, input_k, input_v, embed_list, lengths):
@@ -81,13 +90,6 @@ class RPEMultiHeadAttention(nn.Module):
         H, ch = self.num_heads, self.d_model_per_head
         if input_k.shape != input_q.shape or len(embed_list) != B or len(lengths) != B:
             raise ValueError("lengths: self-attention over a padded stack, one embedding per element")
-        q2 = self.proj_q(input_q).contiguous()
-        k2 = self.proj_k(input_k).contiguous()
-        v2 = self.proj_v(input_v).contiguous()
-        wp = self.proj_p.weight.view(H, ch, C)
-        qh = q2.view(B, N, H, ch)
-        u = torch.einsum('bnhc,hcj->bnhj', qh, wp).contiguous()
-        add = torch.einsum('bnhc,hc->bnh', qh, self.proj_p.bias.view(H, ch)).contiguous()
         hidden = torch.zeros((B, N, C), dtype=torch.float32, device=dev)
         nmax = max(int(n) for n in lengths)
         scores = torch.empty((H, nmax, nmax), dtype=torch.float32, device=dev)   # scratch: the kernel writes it, nobody reads
@@ -100,7 +102,8 @@ class RPEMultiHeadAttention(nn.Module):
                     raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
                 if n == 0:
                     continue
-                _lib.check(L.gr_rpe_attention(_lib.ptr(emb), _lib.ptr(u[b]), _lib.ptr(add[b]), _lib.ptr(q2[b]), _lib.ptr(k2[b]),
-                                              _lib.ptr(v2[b]), None, None, None, n, n, C, H, _lib.ptr(scores),
+                q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
+                _lib.check(L.gr_rpe_attention(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2), _lib.ptr(k2),
+                                              _lib.ptr(v2), None, None, None, n, n, C, H, _lib.ptr(scores),
                                               _lib.ptr(hidden[b]), st))
         return hidden, None

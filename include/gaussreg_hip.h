@@ -340,6 +340,31 @@ int gr_sinkhorn(const float* scores, int64_t batch, int64_t m, int64_t n, const 
  * with n, kernel_points (k,3), weights (k,cin,cout), bias (cout) or null -> out (m,cout).
  * gr_neighbor_pool: kpconv/functional.py maxpool (mode 0, :54-67) / nearest_upsample (mode 1, :6-22). */
 size_t gr_kpconv_workspace_bytes(int64_t n, int64_t m, int64_t k, int64_t cin);
+/* gr_kpconv_plan: which compiled variants gr_kpconv_forward runs for these sizes (host only, touches no GPU;
+ * gr_kpconv_forward dispatches on this very value).  operands_aligned: nonzero when the workspace and `weights` are
+ * 16-byte aligned.  Returns gather | product << 8, or -1 where gr_kpconv_forward launches nothing (m == 0) or refuses
+ * the sizes.  gather = one kernel code (low nibble) plus the branches the generic kernel takes inside; product = one
+ * tile code, plus GR_KP_PRODUCT_ALIGNED for the float4-load form of the three large tiles. */
+enum {
+  GR_KP_GATHER_MFMA_1 = 0,       /* matrix-core gather, cin = 16 (h <= 64, n > 0) */
+  GR_KP_GATHER_MFMA_2 = 1,       /* cin = 32 */
+  GR_KP_GATHER_MFMA_4 = 2,       /* cin = 64 */
+  GR_KP_GATHER_MFMA_8 = 3,       /* cin = 128 */
+  GR_KP_GATHER_MFMA_16 = 4,      /* cin = 256 */
+  GR_KP_GATHER_T64 = 5,          /* generic gather, 64 threads per query (cin <= 64) */
+  GR_KP_GATHER_T128 = 6,         /* 128 threads (cin <= 128) */
+  GR_KP_GATHER_T256 = 7,         /* 256 threads (any other cin) */
+  GR_KP_GATHER_KERNEL_MASK = 15,
+  GR_KP_GATHER_FLUSH = 16,       /* generic: cin > threads, partial sums accumulated in the workspace per channel */
+  GR_KP_GATHER_CHUNKED = 32,     /* generic: h > 256, neighbours staged in several chunks */
+  GR_KP_PRODUCT_SMALL = 0,       /* 64 x 64 tile (m < 128 or cout <= 16) */
+  GR_KP_PRODUCT_128X64 = 1,      /* 16 < cout <= 64 */
+  GR_KP_PRODUCT_64X128 = 2,      /* cout > 64, fewer than 768 tiles of 128 x 128 */
+  GR_KP_PRODUCT_128X128 = 3,     /* cout > 64, 768 tiles or more */
+  GR_KP_PRODUCT_ALIGNED = 4      /* k * cin a multiple of 16, cout a multiple of 4, operands_aligned */
+};
+int gr_kpconv_plan(int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout, int64_t k, int operands_aligned);
+/* n == 0 (s_feats / s_points may be null) and h == 0 (neighbor_indices may be null) give out = bias (zeros without one). */
 int gr_kpconv_forward(const float* s_feats, const float* q_points, const float* s_points,
                       const int64_t* neighbor_indices, int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout,
                       const float* kernel_points, int64_t k, const float* weights, const float* bias, float sigma,

@@ -101,3 +101,16 @@ def assert_rel_scale(got, want, rel=1e-5, what="", mask=None):
     err = float(np.abs(got - want).max()) if want.size else 0.0
     assert err <= rel * scale + 1e-30, f"{what}: max |got - want| = {err:.3e} > {rel:g} x scale {scale:.3g} (= {err / max(scale, 1e-300):.2e} rel)"
     return err / max(scale, 1e-300)
+
+
+def assert_as_exact_as_reference(got, ref32, ref64, factor=8.0, what=""):
+    """The north_star bar, against the EXACT answer: |hip - f64| <= 1e-5 * scale (and the same against the reference's fp32
+    values); plus: the HIP rounding error stays within `factor` of the reference's own fp32 rounding error (the GPU kernels
+    accumulate longer fp32 chains -- e.g. 15 x Cin products per KPConv output -- than ATen's blocked CPU sums)."""
+    got = np.asarray(got, np.float64)
+    e_hip = np.abs(got - ref64).max()
+    e_ref = np.abs(ref32.astype(np.float64) - ref64).max()
+    scale = np.abs(ref64).max()
+    assert e_hip <= 1e-5 * scale, f"{what}: |hip - f64| = {e_hip:.3e}, scale {scale:.3g}"
+    assert np.abs(got - ref32).max() <= 1e-5 * scale, f"{what}: max |hip - ref32| = {np.abs(got - ref32).max():.3e}, scale {scale:.3g}"
+    assert e_hip <= factor * e_ref + 1e-7 * scale, f"{what}: |hip - f64| = {e_hip:.3e} vs |ref32 - f64| = {e_ref:.3e} (scale {scale:.3g})"

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import GOLDEN, assert_neighbors_equal_up_to_ties, load_golden
+from helpers import GOLDEN, assert_as_exact_as_reference, assert_neighbors_equal_up_to_ties, load_golden
 
 sys.path.insert(0, GOLDEN)
 import demo_inputs  # noqa: E402
@@ -33,19 +33,6 @@ def _c(a):
 def same_sum(t, stored):
     """fp64 sum of a regenerated input vs the generator's (the reduction order depends on the host's thread count)."""
     return abs(float(t.double().sum()) - float(stored)) <= 1e-11 * max(1.0, abs(float(stored)))
-
-
-def assert_as_exact_as_reference(got, ref32, ref64, factor=8.0, what=""):
-    """The north_star bar, against the EXACT answer: |hip - f64| <= 1e-5 * scale (and the same against the reference's fp32
-    values); plus: the HIP rounding error stays within `factor` of the reference's own fp32 rounding error (the GPU kernels
-    accumulate longer fp32 chains -- e.g. 15 x Cin products per KPConv output -- than ATen's blocked CPU sums)."""
-    got = np.asarray(got, np.float64)
-    e_hip = np.abs(got - ref64).max()
-    e_ref = np.abs(ref32.astype(np.float64) - ref64).max()
-    scale = np.abs(ref64).max()
-    assert e_hip <= 1e-5 * scale, f"{what}: |hip - f64| = {e_hip:.3e}, scale {scale:.3g}"
-    assert np.abs(got - ref32).max() <= 1e-5 * scale, f"{what}: max |hip - ref32| = {np.abs(got - ref32).max():.3e}, scale {scale:.3g}"
-    assert e_hip <= factor * e_ref + 1e-7 * scale, f"{what}: |hip - f64| = {e_hip:.3e} vs |ref32 - f64| = {e_ref:.3e} (scale {scale:.3g})"
 
 
 @pytest.fixture(scope="module")
