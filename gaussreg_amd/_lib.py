@@ -76,6 +76,10 @@ SIGNATURES.update({
     "gr_raster_backward_aux": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size,
                                        c_void, c_size, c_i64p, c_void, c_void, c_void, c_void, c_void, c_int] +
                                [c_void] * 8 + [c_void, c_size, c_void]),
+    "gr_raster_backward_cam_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p, c_int]),
+    "gr_raster_backward_cam": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size,
+                                       c_void, c_size, c_i64p, c_void, c_void, c_void, c_void, c_void, c_int] +
+                               [c_void] * 11 + [c_void, c_size, c_void]),
 })
 
 

@@ -13,6 +13,10 @@
 //   preprocess bwd 1 thread / Gaussian: per view in order, sums its slots in rectangle order and applies the chain rule in
 //                  fp32 (conic -> cov2D -> cov3D -> scale / quaternion, NDC mean -> mean, SH -> colour), accumulated over
 //                  the views in registers; every output is written once.
+//   camera         (gr_raster_backward_cam) a preprocess bwd kernel of its own that also sums, per view, the 27 non-zero
+//                  entries of dL/d(viewmatrix, projmatrix, campos) over the workgroup (DPP inside the wave, the four waves in
+//                  order through LDS) into per-(view, workgroup) partials; a second kernel adds the partials of a view in a
+//                  fixed order.  No float atomics here either.
 #include <algorithm>
 #include <type_traits>
 
@@ -366,8 +370,30 @@ struct BwdOut {
   float* cov3D;     // (P, 6)
 };
 
+// Camera gradients.  With p_3 = 1, per (view, Gaussian):
+//   ph[c] = sum_j proj[j * 4 + c] p_j (c = 0, 1, 3; column 2 is never read)  ->  dproj[j * 4 + c] = p_j dph[c]
+//   t[c]  = sum_j view[j * 4 + c] p_j (c = 0 .. 2; column 3 is never read)   ->  dview[j * 4 + c] = p_j dt[c], to dt[2] the
+//           depth map adds gs[9] (AUX)
+//   A0[j] = J00 view[j * 4] + J02 view[j * 4 + 2], A1[j] = J11 view[j * 4 + 1] + J12 view[j * 4 + 2], j = 0 .. 2
+//                                          ->  dview[j * 4 + (0, 1, 2)] += (gA0_j J00, gA1_j J11, gA0_j J02 + gA1_j J12)
+//   SH direction = (p - campos) / |.|      ->  dcampos = -(the direction's share of dmean)
+// NCAM = 27 sums per view, in the order of the partials: view (j, c) at 3 j + c, proj (j, c in {0, 1, 3}) at 12 + 3 j + k,
+// campos at 24 + k.  A thread keeps the 18 factors (NCAMF) of a view until the end of that view's iteration, where all 64
+// lanes of the wave are back together (the DPP sums need the whole wave), forms the products there and sums them; a wave
+// in which no lane has a rectangle for the view writes zeros instead.  Per (view, wave) sums wait in LDS (432 bytes per
+// view, dynamic) for the end of the kernel: no barrier inside the view loop.
+constexpr int NCAM = 27;
+constexpr int NCAMF = 18;  // dph0, dph1, dph3; dt[0 .. 2]; the covariance path's 3 x 3; dcampos[0 .. 2]
+
+struct PreBwdCam {
+  float* partial;  // [V][gridDim.x][NCAM]
+};
+
 // AUX: the slots hold NF_AUX floats; the tenth, dL/dz, reaches the mean through the third row of the view matrix
 // (z = view[2] p0 + view[6] p1 + view[10] p2 + view[14]).
+// CAM: threads past P stay (as lanes that have no rectangle in any view) until the sums are done.
+// The body (preprocess_backward_body.hpp) is included in preprocess_backward_kernel (CAM = false: the kernel as it was)
+// and in preprocess_backward_cam_kernel (CAM = true), a kernel of its own.
 template <bool HAS_SH, bool HAS_COV, bool AUX = false>
 __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     int P, int D, int M, int V, int W, int H, const DevView* __restrict__ views, const float* __restrict__ means3D,
@@ -375,230 +401,55 @@ __global__ __launch_bounds__(256) void preprocess_backward_kernel(
     const float* __restrict__ cov3D_precomp, const uint32_t* __restrict__ rect_raw, const float4* __restrict__ rec,
     const int32_t* __restrict__ slot_local, const int32_t* __restrict__ block_pre, int64_t slot_cap,
     const float* __restrict__ slots, BwdOut out) {
-  constexpr int NF = AUX ? NF_AUX : gr::NF;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  const int K = (D + 1) * (D + 1);
-  const float p[3] = {means3D[3 * (int64_t)i], means3D[3 * (int64_t)i + 1], means3D[3 * (int64_t)i + 2]};
-  float sc[3] = {0.f, 0.f, 0.f}, rot[4] = {0.f, 0.f, 0.f, 0.f}, c6[6];
-  if (HAS_COV) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * (int64_t)i + k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) sc[k] = scales[3 * (int64_t)i + k];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) rot[k] = rotations[4 * (int64_t)i + k];
+  constexpr bool CAM = false;
+  const PreBwdCam cam_out{nullptr};  // (never read)
+#define GR_PREPROCESS_BACKWARD_BODY_OK
+#include "preprocess_backward_body.hpp"
+#undef GR_PREPROCESS_BACKWARD_BODY_OK
+}
+
+// + the camera sums; dynamic LDS: 4 * NCAM floats per view
+template <bool HAS_SH, bool HAS_COV, bool AUX>
+__global__ __launch_bounds__(256) void preprocess_backward_cam_kernel(
+    int P, int D, int M, int V, int W, int H, const DevView* __restrict__ views, const float* __restrict__ means3D,
+    const float* __restrict__ shs, const float* __restrict__ scales, const float* __restrict__ rotations,
+    const float* __restrict__ cov3D_precomp, const uint32_t* __restrict__ rect_raw, const float4* __restrict__ rec,
+    const int32_t* __restrict__ slot_local, const int32_t* __restrict__ block_pre, int64_t slot_cap,
+    const float* __restrict__ slots, BwdOut out, PreBwdCam cam_out) {
+  constexpr bool CAM = true;
+#define GR_PREPROCESS_BACKWARD_BODY_OK
+#include "preprocess_backward_body.hpp"
+#undef GR_PREPROCESS_BACKWARD_BODY_OK
+}
+
+// one workgroup per view: the partials of the view's nb workgroups, summed in a fixed order (row r of 32 takes workgroups
+// r, r + 32, ... in order; then the 32 rows in order).  Columns the forward never reads (3 of viewmatrix, 2 of
+// projmatrix) get zeros.  Null outputs are not written.
+__global__ __launch_bounds__(1024) void camera_sum_kernel(int nb, const float* __restrict__ partial, float* __restrict__ dview,
+                                                          float* __restrict__ dproj, float* __restrict__ dcampos) {
+  __shared__ float s_row[32][32];
+  __shared__ float s_tot[NCAM];
+  const int v = blockIdx.x, f = threadIdx.x & 31, r = threadIdx.x >> 5;
+  float acc = 0.0f;
+  if (f < NCAM) {
+    const float* src = partial + (int64_t)v * nb * NCAM + f;
+    for (int b = r; b < nb; b += 32) acc += src[(int64_t)b * NCAM];
   }
-  float shr[HAS_SH ? 48 : 1], dsh[HAS_SH ? 48 : 1];
-  if (HAS_SH) {
-#pragma unroll
-    for (int k = 0; k < 48; ++k) {
-      shr[k] = k < 3 * K ? shs[(int64_t)i * M * 3 + k] : 0.0f;
-      dsh[k] = 0.0f;
-    }
+  s_row[r][f] = acc;
+  __syncthreads();
+  if (threadIdx.x < NCAM) {
+    float t = 0.0f;
+    for (int k = 0; k < 32; ++k) t += s_row[k][threadIdx.x];
+    s_tot[threadIdx.x] = t;
   }
-  float dmean[3] = {0.f, 0.f, 0.f}, dcol[3] = {0.f, 0.f, 0.f}, dop = 0.f, dscale[3] = {0.f, 0.f, 0.f};
-  float drot[4] = {0.f, 0.f, 0.f, 0.f}, dcov[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int v = 0; v < V; ++v) {
-    const int64_t o = (int64_t)v * P + i;
-    const int64_t vbase = (int64_t)v * P;
-    float* m2 = out.means2D != nullptr ? out.means2D + 3 * o : nullptr;
-    int x0, y0, w, h;
-    const uint32_t rr = rect_raw[o];
-    if (rr == 0u || !rect_decode(rr, i, vbase, rec, gx, gy, x0, y0, w, h)) {
-      if (m2) m2[0] = m2[1] = m2[2] = 0.0f;
-      continue;
-    }
-    // this (view, Gaussian)'s slots, in rectangle order
-    const int64_t s0 = (int64_t)slot_local[o] + block_pre[o >> 8];
-    const int n = w * h;
-    float gs[NF];
-#pragma unroll
-    for (int f = 0; f < NF; ++f) gs[f] = 0.0f;
-    for (int k = 0; k < n; ++k) {
-      if (s0 + k >= slot_cap) break;  // (never: see render_backward_kernel)
-      const float* s = slots + NF * (s0 + k);
-#pragma unroll
-      for (int f = 0; f < NF; ++f) gs[f] += s[f];
-    }
-    const DevView& cam = views[v];
-    // ---- forward quantities (same fp32 operations as preprocess_kernel)
-    float pv[3], ph[4];
-    xform4x3(cam.view, p, pv);
-    xform4x4(cam.proj, p, ph);
-    const float pw = 1.0f / (ph[3] + 0.0000001f);
-    if (!HAS_COV) cov3d_from_scale_rot(sc, cam.scale_mod, rot, c6);
-    const float tz = pv[2];
-    const float limx = 1.3f * cam.tanx, limy = 1.3f * cam.tany;
-    const float ux = pv[0] / tz, uy = pv[1] / tz;
-    const float cux = fminf(limx, fmaxf(-limx, ux)), cuy = fminf(limy, fmaxf(-limy, uy));
-    const float txp = cux * tz, typ = cuy * tz;
-    const float J00 = cam.fx / tz, J02 = -(cam.fx * txp) / (tz * tz);
-    const float J11 = cam.fy / tz, J12 = -(cam.fy * typ) / (tz * tz);
-    const float* Vm = cam.view;
-    float A0[3], A1[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      A0[j] = fmaf(J00, Vm[j * 4 + 0], J02 * Vm[j * 4 + 2]);
-      A1[j] = fmaf(J11, Vm[j * 4 + 1], J12 * Vm[j * 4 + 2]);
-    }
-    const float S[3][3] = {{c6[0], c6[1], c6[2]}, {c6[1], c6[3], c6[4]}, {c6[2], c6[4], c6[5]}};
-    float SA0[3], SA1[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      SA0[k] = fmaf(S[k][0], A0[0], fmaf(S[k][1], A0[1], S[k][2] * A0[2]));
-      SA1[k] = fmaf(S[k][0], A1[0], fmaf(S[k][1], A1[1], S[k][2] * A1[2]));
-    }
-    const float a = fmaf(A0[0], SA0[0], fmaf(A0[1], SA0[1], A0[2] * SA0[2])) + 0.3f;
-    const float b = fmaf(A1[0], SA0[0], fmaf(A1[1], SA0[1], A1[2] * SA0[2]));
-    const float c = fmaf(A1[0], SA1[0], fmaf(A1[1], SA1[1], A1[2] * SA1[2])) + 0.3f;
-    // ---- conic (c, -b, a) / det -> 2-D covariance
-    const float det = a * c - b * b;
-    const float inv2 = 1.0f / (det * det);
-    const float gA = gs[2], gB = gs[3], gC = gs[4];
-    const float ga = (-c * c * gA + b * c * gB - b * b * gC) * inv2;
-    const float gb = (2.f * b * c * gA - (a * c + b * b) * gB + 2.f * a * b * gC) * inv2;
-    const float gc = (-b * b * gA + a * b * gB - a * a * gC) * inv2;
-    // ---- 2-D covariance = A S A^T -> 3-D covariance and A = J W
-    float dc6[6];
-    dc6[0] = A0[0] * A0[0] * ga + A1[0] * A0[0] * gb + A1[0] * A1[0] * gc;
-    dc6[3] = A0[1] * A0[1] * ga + A1[1] * A0[1] * gb + A1[1] * A1[1] * gc;
-    dc6[5] = A0[2] * A0[2] * ga + A1[2] * A0[2] * gb + A1[2] * A1[2] * gc;
-    dc6[1] = 2.f * A0[0] * A0[1] * ga + (A1[0] * A0[1] + A1[1] * A0[0]) * gb + 2.f * A1[0] * A1[1] * gc;
-    dc6[2] = 2.f * A0[0] * A0[2] * ga + (A1[0] * A0[2] + A1[2] * A0[0]) * gb + 2.f * A1[0] * A1[2] * gc;
-    dc6[4] = 2.f * A0[1] * A0[2] * ga + (A1[1] * A0[2] + A1[2] * A0[1]) * gb + 2.f * A1[1] * A1[2] * gc;
-    float dJ00 = 0.f, dJ02 = 0.f, dJ11 = 0.f, dJ12 = 0.f;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const float gA0 = 2.f * ga * SA0[j] + gb * SA1[j];
-      const float gA1 = gb * SA0[j] + 2.f * gc * SA1[j];
-      dJ00 += gA0 * Vm[j * 4 + 0];
-      dJ02 += gA0 * Vm[j * 4 + 2];
-      dJ11 += gA1 * Vm[j * 4 + 1];
-      dJ12 += gA1 * Vm[j * 4 + 2];
-    }
-    // J -> view-space mean t (the 1.3 tan(fov) clamp of x/z, y/z masks d/dt_x, d/dt_y where active)
-    const float tz2 = tz * tz, tz3 = tz2 * tz;
-    const float dtxp = -cam.fx / tz2 * dJ02, dtyp = -cam.fy / tz2 * dJ12;
-    float dt[3];
-    dt[2] = -cam.fx / tz2 * dJ00 - cam.fy / tz2 * dJ11 + 2.f * cam.fx * txp / tz3 * dJ02 + 2.f * cam.fy * typ / tz3 * dJ12;
-    const bool inx = ux >= -limx && ux <= limx, iny = uy >= -limy && uy <= limy;
-    dt[0] = inx ? dtxp : 0.0f;
-    dt[1] = iny ? dtyp : 0.0f;
-    if (!inx) dt[2] += dtxp * cux;
-    if (!iny) dt[2] += dtyp * cuy;
-    // ---- NDC mean (means2D.grad: dL/dNDC, upstream's 0.5 W / 0.5 H factors) -> homogeneous projection
-    const float dnx = gs[0] * (0.5f * (float)W), dny = gs[1] * (0.5f * (float)H);
-    if (m2) m2[0] = dnx, m2[1] = dny, m2[2] = 0.0f;
-    const float dph0 = dnx * pw, dph1 = dny * pw;
-    const float dph3 = -(dnx * ph[0] + dny * ph[1]) * pw * pw;
-    const float* Pm = cam.proj;
-#pragma unroll
-    for (int j = 0; j < 3; ++j)
-      dmean[j] += Pm[j * 4 + 0] * dph0 + Pm[j * 4 + 1] * dph1 + Pm[j * 4 + 3] * dph3 +
-                  Vm[j * 4 + 0] * dt[0] + Vm[j * 4 + 1] * dt[1] + Vm[j * 4 + 2] * dt[2];
-    if constexpr (AUX) {
-#pragma unroll
-      for (int j = 0; j < 3; ++j) dmean[j] += gs[9] * Vm[j * 4 + 2];
-    }
-    dop += gs[5];
-    // ---- colour
-    if (HAS_SH) {
-      float rgb[3];
-      sh_to_rgb(D, p, cam.campos, [&](int k, int ch) { return shr[k * 3 + ch]; }, rgb);  // the forward's clamp decision
-      const float d0 = p[0] - cam.campos[0], d1 = p[1] - cam.campos[1], d2 = p[2] - cam.campos[2];
-      const float len = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-      const float x = d0 / len, y = d1 / len, z = d2 / len;
-      float B[16], Bx[16], By[16], Bz[16];
-      sh_basis_grad(D, x, y, z, B, Bx, By, Bz);
-      float ddx = 0.f, ddy = 0.f, ddz = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        const float gcol = rgb[ch] > 0.0f ? gs[6 + ch] : 0.0f;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-          dsh[k * 3 + ch] += B[k] * gcol;
-          ddx += Bx[k] * shr[k * 3 + ch] * gcol;
-          ddy += By[k] * shr[k * 3 + ch] * gcol;
-          ddz += Bz[k] * shr[k * 3 + ch] * gcol;
-        }
-      }
-      const float dot = x * ddx + y * ddy + z * ddz;
-      dmean[0] += (ddx - x * dot) / len;
-      dmean[1] += (ddy - y * dot) / len;
-      dmean[2] += (ddz - z * dot) / len;
-    } else {
-      dcol[0] += gs[6];
-      dcol[1] += gs[7];
-      dcol[2] += gs[8];
-    }
-    // ---- 3-D covariance
-    if (HAS_COV) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) dcov[k] += dc6[k];
-    } else {
-      const float mod = cam.scale_mod;
-      const float s[3] = {mod * sc[0], mod * sc[1], mod * sc[2]};
-      const float r = rot[0], x = rot[1], y = rot[2], z = rot[3];
-      float R[3][3];
-      R[0][0] = 1.f - 2.f * (y * y + z * z);
-      R[0][1] = 2.f * (x * y - r * z);
-      R[0][2] = 2.f * (x * z + r * y);
-      R[1][0] = 2.f * (x * y + r * z);
-      R[1][1] = 1.f - 2.f * (x * x + z * z);
-      R[1][2] = 2.f * (y * z - r * x);
-      R[2][0] = 2.f * (x * z - r * y);
-      R[2][1] = 2.f * (y * z + r * x);
-      R[2][2] = 1.f - 2.f * (x * x + y * y);
-      // Sigma = Mt^T Mt with Mt[k][i] = s_k R[i][k]; symmetric upstream gradient Gs (off-diagonals carry half of dc6)
-      const float Gs[3][3] = {{dc6[0], 0.5f * dc6[1], 0.5f * dc6[2]},
-                              {0.5f * dc6[1], dc6[3], 0.5f * dc6[4]},
-                              {0.5f * dc6[2], 0.5f * dc6[4], dc6[5]}};
-      float dR[3][3];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        float ds = 0.f;
-#pragma unroll
-        for (int ii = 0; ii < 3; ++ii) {
-          float dM = 0.f;  // dL/dMt[k][ii] = 2 sum_j Mt[k][j] Gs[j][ii]
-#pragma unroll
-          for (int j = 0; j < 3; ++j) dM += s[k] * R[j][k] * Gs[j][ii];
-          dM *= 2.f;
-          ds += dM * R[ii][k];
-          dR[ii][k] = s[k] * dM;
-        }
-        dscale[k] += mod * ds;
-      }
-      drot[0] += 2.f * (-z * dR[0][1] + y * dR[0][2] + z * dR[1][0] - x * dR[1][2] - y * dR[2][0] + x * dR[2][1]);
-      drot[1] += 2.f * (y * dR[0][1] + z * dR[0][2] + y * dR[1][0] - 2.f * x * dR[1][1] - r * dR[1][2] + z * dR[2][0] +
-                        r * dR[2][1] - 2.f * x * dR[2][2]);
-      drot[2] += 2.f * (-2.f * y * dR[0][0] + x * dR[0][1] + r * dR[0][2] + x * dR[1][0] + z * dR[1][2] - r * dR[2][0] +
-                        z * dR[2][1] - 2.f * y * dR[2][2]);
-      drot[3] += 2.f * (-2.f * z * dR[0][0] - r * dR[0][1] + x * dR[0][2] + r * dR[1][0] - 2.f * z * dR[1][1] + y * dR[1][2] +
-                        x * dR[2][0] + y * dR[2][1]);
-    }
-  }
-  if (out.means3D)
-    for (int k = 0; k < 3; ++k) out.means3D[3 * (int64_t)i + k] = dmean[k];
-  if (out.opacity) out.opacity[i] = dop;
-  if (HAS_SH && out.shs) {
-    float* dst = out.shs + (int64_t)i * M * 3;
-#pragma unroll
-    for (int k = 0; k < 48; ++k)
-      if (k < 3 * M) dst[k] = dsh[k];
-    for (int k = 48; k < 3 * M; ++k) dst[k] = 0.0f;  // coefficients past degree 3
-  }
-  if (!HAS_SH && out.colors)
-    for (int k = 0; k < 3; ++k) out.colors[3 * (int64_t)i + k] = dcol[k];
-  if (HAS_COV && out.cov3D)
-    for (int k = 0; k < 6; ++k) out.cov3D[6 * (int64_t)i + k] = dcov[k];
-  if (!HAS_COV) {
-    if (out.scales)
-      for (int k = 0; k < 3; ++k) out.scales[3 * (int64_t)i + k] = dscale[k];
-    if (out.rotations)
-      for (int k = 0; k < 4; ++k) out.rotations[4 * (int64_t)i + k] = drot[k];
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t < 16) {
+    const int j = t >> 2, c = t & 3;
+    if (dview) dview[v * 16 + t] = c < 3 ? s_tot[3 * j + c] : 0.0f;
+    if (dproj) dproj[v * 16 + t] = c == 2 ? 0.0f : s_tot[12 + 3 * j + (c == 3 ? 2 : c)];
+  } else if (t < 19 && dcampos) {
+    dcampos[v * 3 + (t - 16)] = s_tot[24 + (t - 16)];
   }
 }
 
@@ -606,15 +457,17 @@ struct BwdScratch {
   int32_t* slot_local;  // [V * P]
   int32_t* block_pre;   // [ceil(V * P / 256)]
   float* slots;         // [R][NF] (NF_AUX for gr_raster_backward_aux)
+  float* cam_partial;   // [V][ceil(P / 256)][NCAM] (gr_raster_backward_cam only)
   size_t bytes;
 };
 
-BwdScratch carve_bwd(void* p, int64_t P, int V, int64_t R, int nf = NF) {
+BwdScratch carve_bwd(void* p, int64_t P, int V, int64_t R, int nf = NF, bool cam = false) {
   BwdScratch s;
   Carver c(p);
   s.slot_local = c.take<int32_t>(P * V);
   s.block_pre = c.take<int32_t>((P * V + 255) / 256 + 1);  // + the grand total
   s.slots = c.take<float>(R * nf);
+  s.cam_partial = cam ? c.take<float>((P + 255) / 256 * V * NCAM) : nullptr;
   s.bytes = c.used();
   return s;
 }
@@ -641,8 +494,24 @@ extern "C" size_t gr_raster_backward_aux_bytes(int64_t P, int num_views, int wid
   return carve_bwd(nullptr, P, num_views, total_rendered(h_num_rendered, num_views), NF_AUX).bytes;
 }
 
+extern "C" size_t gr_raster_backward_cam_bytes(int64_t P, int num_views, int width, int height,
+                                               const int64_t* h_num_rendered, int flags) {
+  if (P < 0 || num_views < 1 || width <= 0 || height <= 0 || h_num_rendered == nullptr) return 0;
+  const int nf = (flags & GR_RASTER_BWD_COLOR_ONLY) ? NF : NF_AUX;
+  return carve_bwd(nullptr, P, num_views, total_rendered(h_num_rendered, num_views), nf, true).bytes;
+}
+
+// the three camera outputs of gr_raster_backward_cam, each nullable; all null: the instances without camera sums run
+struct CamGrads {
+  float* view = nullptr;    // (V, 16)
+  float* proj = nullptr;    // (V, 16)
+  float* campos = nullptr;  // (V, 3)
+  bool any() const { return view != nullptr || proj != nullptr || campos != nullptr; }
+};
+
 // aux: gr_raster_backward_aux -- ten floats per slot, gradients of the depth and alpha maps; any map gradient may be null
-static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalpha, int64_t P, int M, const float* means3D,
+static int backward_impl(bool aux, const CamGrads& cam, const float* dL_ddepth, const float* dL_dalpha, int64_t P, int M,
+                         const float* means3D,
                          const float* shs, const float* colors_precomp, const float* opacities, const float* scales,
                          const float* rotations, const float* cov3D_precomp, const gr_raster_view* h_views, int num_views,
                          const void* geom, size_t geom_bytes, const void* bin, size_t bin_bytes,
@@ -659,7 +528,12 @@ static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalph
     GR_REQUIRE(h_views[v].image_width == W && h_views[v].image_height == H && h_views[v].sh_degree == D,
                "all views of one call must share image size and sh_degree");
   GR_REQUIRE(W > 0 && H > 0 && D >= 0 && D <= 3, "bad image size or sh_degree");
-  if (P == 0) return GR_OK;
+  if (P == 0) {
+    if (cam.view) GR_HIP(hipMemsetAsync(cam.view, 0, sizeof(float) * 16 * num_views, stream));
+    if (cam.proj) GR_HIP(hipMemsetAsync(cam.proj, 0, sizeof(float) * 16 * num_views, stream));
+    if (cam.campos) GR_HIP(hipMemsetAsync(cam.campos, 0, sizeof(float) * 3 * num_views, stream));
+    return GR_OK;
+  }
   GR_REQUIRE(means3D != nullptr, "means3D is null");
   GR_REQUIRE((shs != nullptr) != (colors_precomp != nullptr), "exactly one of shs / colors_precomp");
   GR_REQUIRE((scales != nullptr && rotations != nullptr) != (cov3D_precomp != nullptr),
@@ -675,7 +549,7 @@ static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalph
   GR_REQUIRE(R == 0 || (bin != nullptr && bin_bytes >= bn.bytes), "binning buffer missing or too small");
   GR_REQUIRE(R == 0 || (final_T != nullptr && n_contrib != nullptr && (aux || dL_dcolor != nullptr)), "null per-pixel state");
   const int nf = aux ? NF_AUX : NF;
-  const BwdScratch s = carve_bwd(scratch, P, num_views, R, nf);
+  const BwdScratch s = carve_bwd(scratch, P, num_views, R, nf, cam.any());
   if (!scratch || scratch_bytes < s.bytes) {
     set_error("raster backward scratch too small: need %zu bytes, got %zu", s.bytes, scratch_bytes);
     return GR_ERR_WORKSPACE;
@@ -718,10 +592,18 @@ static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalph
   {
     KernelTimer timer("raster_bwd_preprocess", stream);
     const dim3 grd((unsigned)((P + 255) / 256)), blk(256);
+    const size_t cam_lds = sizeof(float) * NCAM * 4 * num_views;  // (at most 27 648 bytes: num_views <= MAX_VIEWS)
 #define GR_PBWD_(SH, COV, AUX)                                                                                            \
-  hipLaunchKernelGGL((preprocess_backward_kernel<SH, COV, AUX>), grd, blk, 0, stream, (int)P, D, M, num_views, W, H,      \
-                     g.views, means3D, shs, scales, rotations, cov3D_precomp, g.rect_raw, g.rec, s.slot_local,            \
-                     s.block_pre, R, s.slots, out)
+  do {                                                                                                                    \
+    if (cam.any())                                                                                                        \
+      hipLaunchKernelGGL((preprocess_backward_cam_kernel<SH, COV, AUX>), grd, blk, cam_lds, stream, (int)P, D, M,         \
+                         num_views, W, H, g.views, means3D, shs, scales, rotations, cov3D_precomp, g.rect_raw, g.rec,     \
+                         s.slot_local, s.block_pre, R, s.slots, out, PreBwdCam{s.cam_partial});                     \
+    else                                                                                                                  \
+      hipLaunchKernelGGL((preprocess_backward_kernel<SH, COV, AUX>), grd, blk, 0, stream, (int)P, D, M, num_views, W, H,  \
+                         g.views, means3D, shs, scales, rotations, cov3D_precomp, g.rect_raw, g.rec, s.slot_local,        \
+                         s.block_pre, R, s.slots, out);                                                                   \
+  } while (0)
 #define GR_PBWD(SH, COV) do { if (aux) GR_PBWD_(SH, COV, true); else GR_PBWD_(SH, COV, false); } while (0)
     if (shs && cov3D_precomp) GR_PBWD(true, true);
     else if (shs) GR_PBWD(true, false);
@@ -730,6 +612,11 @@ static int backward_impl(bool aux, const float* dL_ddepth, const float* dL_dalph
 #undef GR_PBWD
 #undef GR_PBWD_
     GR_LAUNCH_CHECK();
+    if (cam.any()) {
+      hipLaunchKernelGGL(camera_sum_kernel, dim3((unsigned)num_views), dim3(1024), 0, stream, (int)grd.x, s.cam_partial,
+                         cam.view, cam.proj, cam.campos);
+      GR_LAUNCH_CHECK();
+    }
   }
   (void)opacities;
   return GR_OK;
@@ -743,7 +630,7 @@ extern "C" int gr_raster_backward(int64_t P, int M, const float* means3D, const 
                                   float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
                                   float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                                   void* scratch, size_t scratch_bytes, void* stream_) {
-  return backward_impl(false, nullptr, nullptr, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
+  return backward_impl(false, CamGrads{}, nullptr, nullptr, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
                        cov3D_precomp, h_views, num_views, geom, geom_bytes, bin, bin_bytes, h_num_rendered, final_T, n_contrib,
                        dL_dcolor, flags, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
                        dL_drotations, dL_dcov3D, scratch, scratch_bytes, stream_);
@@ -758,8 +645,31 @@ extern "C" int gr_raster_backward_aux(int64_t P, int M, const float* means3D, co
                                       float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
                                       float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
                                       void* scratch, size_t scratch_bytes, void* stream_) {
-  return backward_impl(true, dL_ddepth, dL_dalpha, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
+  return backward_impl(true, CamGrads{}, dL_ddepth, dL_dalpha, P, M, means3D, shs, colors_precomp, opacities, scales, rotations,
                        cov3D_precomp, h_views, num_views, geom, geom_bytes, bin, bin_bytes, h_num_rendered, final_T, n_contrib,
                        dL_dcolor, flags, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity, dL_dscales,
                        dL_drotations, dL_dcov3D, scratch, scratch_bytes, stream_);
+}
+
+extern "C" int gr_raster_backward_cam(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                                      const float* opacities, const float* scales, const float* rotations,
+                                      const float* cov3D_precomp, const gr_raster_view* h_views, int num_views,
+                                      const void* geom, size_t geom_bytes, const void* bin, size_t bin_bytes,
+                                      const int64_t* h_num_rendered, const float* final_T, const int32_t* n_contrib,
+                                      const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha, int flags,
+                                      float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
+                                      float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                                      float* dL_dviewmatrix, float* dL_dprojmatrix, float* dL_dcampos, void* scratch,
+                                      size_t scratch_bytes, void* stream_) {
+  const bool colour_only = (flags & GR_RASTER_BWD_COLOR_ONLY) != 0;
+  if (colour_only && (dL_ddepth != nullptr || dL_dalpha != nullptr)) {
+    set_error("gr_raster_backward_cam: GR_RASTER_BWD_COLOR_ONLY takes no dL_ddepth / dL_dalpha");
+    return GR_ERR_INVALID;
+  }
+  CamGrads cam;
+  cam.view = dL_dviewmatrix, cam.proj = dL_dprojmatrix, cam.campos = dL_dcampos;
+  return backward_impl(!colour_only, cam, dL_ddepth, dL_dalpha, P, M, means3D, shs, colors_precomp, opacities, scales,
+                       rotations, cov3D_precomp, h_views, num_views, geom, geom_bytes, bin, bin_bytes, h_num_rendered,
+                       final_T, n_contrib, dL_dcolor, flags, dL_dmeans3D, dL_dmeans2D, dL_dshs, dL_dcolors, dL_dopacity,
+                       dL_dscales, dL_drotations, dL_dcov3D, scratch, scratch_bytes, stream_);
 }

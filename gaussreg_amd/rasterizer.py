@@ -16,7 +16,16 @@ throughput path: per-Gaussian inputs are read once per batch).
 Differentiable like upstream: when grad mode is on and an input requires grad, the call goes through an autograd
 Function (_RasterizeViews) whose backward is the HIP backward of include/gaussreg_hip.h (gr_raster_backward): gradients
 for means3D, means2D (dL/dNDC), shs / colors_precomp, opacities, scales / rotations / cov3D_precomp; radii is not
-differentiable, cameras get none.  Otherwise every call takes the forward-only path, unchanged.
+differentiable.  Otherwise every call takes the forward-only path, unchanged.
+
+Cameras: `viewmatrix`, `projmatrix` and `campos` of every view are differentiable too (gr_raster_backward_cam), as three
+INDEPENDENT inputs, exactly as the settings present them: the gradient of `viewmatrix` does not include what reaches the
+image through `projmatrix` or `campos`.  A caller that builds the three from one pose in torch (gaussreg_amd/pose.py) gets
+the pose gradient by autograd's chain rule.  Element [j][c] of a matrix gradient belongs to element [j][c] of the tensor,
+whatever its strides, dtype or device; column 3 of viewmatrix and column 2 of projmatrix are never read by the forward and
+get zeros, campos acts through the SH view direction only (zeros with colors_precomp).  tanfovx, tanfovy, scale_modifier
+and bg get no gradient.  A camera tensor that requires grad is enough to take the autograd path; with none, every path
+and every result is what it is without this feature.
 """
 import ctypes
 import os
@@ -46,6 +55,7 @@ class GaussianRasterizationSettings(NamedTuple):
 FAST_EXP = 1  # GR_RASTER_FAST_EXP (include/gaussreg_hip.h)
 SPLIT = 2     # GR_RASTER_SPLIT
 SHARE = 4     # GR_RASTER_SHARE
+BWD_COLOR_ONLY = 8  # GR_RASTER_BWD_COLOR_ONLY
 _ENV_FAST = None
 _bin_hint = {}  # (device, P, V, W, H) -> (bytes of the binning buffer, largest chunk) the last call of that shape needed
 
@@ -91,6 +101,23 @@ class ViewBatch:
         self.count = len(settings)
         self.height, self.width = int(settings[0].image_height), int(settings[0].image_width)
         self.array = (_lib.RasterView * self.count)(*[_view_struct(s) for s in settings])
+        # the tensors the cameras were read from: a call under grad mode returns their gradients to them
+        self.cameras = tuple((s.viewmatrix, s.projmatrix, s.campos) for s in settings)
+
+    def wants_grad(self):
+        return torch.is_grad_enabled() and any(t.requires_grad for cam in self.cameras for t in cam)
+
+    def camera_inputs(self, dev):
+        """Stacked (V,4,4), (V,4,4), (V,3) fp32 tensors on `dev`, differentiable functions of the settings' tensors (None
+        where no view's tensor requires grad).  Their values are not read: the kernels take the marshalled copy."""
+        out = []
+        for k, shape in enumerate(((4, 4), (4, 4), (3,))):
+            ts = [cam[k] for cam in self.cameras]
+            if not any(t.requires_grad for t in ts):
+                out.append(None)
+                continue
+            out.append(torch.stack([t.to(device=dev, dtype=torch.float32).reshape(shape) for t in ts]))
+        return out
 
 
 def _dev_f32(t: Optional[torch.Tensor], dev, name):
@@ -210,10 +237,12 @@ def _dev_f32_grad(t, dev):
 
 class _RasterizeViews(torch.autograd.Function):
     """Autograd forward (gr_raster_preprocess + gr_raster_render_keep, serial, on the caller's stream) and HIP backward
-    (gr_raster_backward).  Inputs arrive as fp32, contiguous, on the device (converted differentiably by the caller)."""
+    (gr_raster_backward).  Inputs arrive as fp32, contiguous, on the device (converted differentiably by the caller).
+    vmat / pmat / cpos: ViewBatch.camera_inputs, present only when a camera tensor requires grad; the backward then is
+    gr_raster_backward_cam."""
 
     @staticmethod
-    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov):
+    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov, vmat=None, pmat=None, cpos=None):
         dev = m.device
         L = _lib.lib()
         V, views, H, W = vb.count, vb.array, vb.height, vb.width
@@ -262,23 +291,44 @@ class _RasterizeViews(torch.autograd.Function):
         dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
                                              out(cov, 11))
         dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
+        dcam = _camera_outputs(need, V, dev)
         hw = H * W
         final_T = ctx.state[:V * hw]
         n_contrib = ctx.state[V * hw:]
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
-            sbytes = L.gr_raster_backward_bytes(P, V, W, H, ctx.nr) + 256
-            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.gr_raster_backward(
-                P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov),
-                vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(), ctx.nr,
-                _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), ctx.flags, _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh),
-                _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov), _lib.ptr(scratch),
-                scratch.numel(), st))
+            if dcam is not None:
+                sbytes = L.gr_raster_backward_cam_bytes(P, V, W, H, ctx.nr, BWD_COLOR_ONLY) + 256
+                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.gr_raster_backward_cam(
+                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
+                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
+                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), None, None, ctx.flags | BWD_COLOR_ONLY,
+                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
+                    _lib.ptr(dcov), _lib.ptr(dcam[0]), _lib.ptr(dcam[1]), _lib.ptr(dcam[2]), _lib.ptr(scratch),
+                    scratch.numel(), st))
+            else:
+                sbytes = L.gr_raster_backward_bytes(P, V, W, H, ctx.nr) + 256
+                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.gr_raster_backward(
+                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
+                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
+                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), ctx.flags, _lib.ptr(dm), _lib.ptr(dm2),
+                    _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov),
+                    _lib.ptr(scratch), scratch.numel(), st))
         if dm2 is not None:
             shape, dtype, device = ctx.m2d
             dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
-        return None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov
+        return (None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov) + (dcam or (None, None, None))
+
+
+def _camera_outputs(need, V, dev):
+    """Gradient buffers for the camera inputs (positions 12 .. 14 of the autograd Functions) that need one; None when
+    none does: the backward then is the call without camera gradients."""
+    if len(need) < 15 or not any(need[12:15]):
+        return None
+    return tuple(torch.empty((V,) + shape, dtype=torch.float32, device=dev) if need[12 + k] else None
+                 for k, shape in enumerate(((4, 4), (4, 4), (3,))))
 
 
 def _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, keep):
@@ -313,7 +363,7 @@ class _RasterizeViewsAux(torch.autograd.Function):
     gr_raster_backward_aux.  Output gradients autograd did not produce are passed as null pointers."""
 
     @staticmethod
-    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov):
+    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov, vmat=None, pmat=None, cpos=None):
         color, radii, depth, alpha, nr, M, geom, binb, state = _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, True)
         ctx.vb, ctx.flags, ctx.M, ctx.nr = vb, flags, M, nr
         ctx.geom, ctx.binb, ctx.state = geom, binb, state
@@ -343,23 +393,35 @@ class _RasterizeViewsAux(torch.autograd.Function):
         dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
                                              out(cov, 11))
         dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
+        dcam = _camera_outputs(need, V, dev)
         hw = H * W
         final_T = ctx.state[:V * hw]
         n_contrib = ctx.state[V * hw:]
         with torch.cuda.device(dev):
             st = _lib.stream_ptr(dev)
-            sbytes = L.gr_raster_backward_aux_bytes(P, V, W, H, ctx.nr) + 256
-            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-            _lib.check(L.gr_raster_backward_aux(
-                P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov),
-                vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(), ctx.nr,
-                _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags, _lib.ptr(dm),
-                _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov),
-                _lib.ptr(scratch), scratch.numel(), st))
+            if dcam is not None:
+                sbytes = L.gr_raster_backward_cam_bytes(P, V, W, H, ctx.nr, 0) + 256
+                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.gr_raster_backward_cam(
+                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
+                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
+                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags,
+                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
+                    _lib.ptr(dcov), _lib.ptr(dcam[0]), _lib.ptr(dcam[1]), _lib.ptr(dcam[2]), _lib.ptr(scratch),
+                    scratch.numel(), st))
+            else:
+                sbytes = L.gr_raster_backward_aux_bytes(P, V, W, H, ctx.nr) + 256
+                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+                _lib.check(L.gr_raster_backward_aux(
+                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
+                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
+                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags,
+                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
+                    _lib.ptr(dcov), _lib.ptr(scratch), scratch.numel(), st))
         if dm2 is not None:
             shape, dtype, device = ctx.m2d
             dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
-        return None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov
+        return (None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov) + (dcam or (None, None, None))
 
 
 def _wants_grad(*ts):
@@ -383,7 +445,8 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     (`_one`: internal, one camera -- the outputs come back as (3,H,W) and (P,), no view ops on the way out.)
 
     Autograd: when grad mode is on and any input requires grad, the call is differentiable (see the module docstring);
-    it then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
+    the `viewmatrix`, `projmatrix` and `campos` tensors of the settings (or of the settings a ViewBatch was built from)
+    count as inputs.  It then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
     `means2D` (keyword only, extension): a (V, P, 3) tensor (upstream's (P, 3) screen-space means for one camera) whose
     .grad receives dL/d(NDC position) per view; its values are not read.
 
@@ -406,7 +469,8 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     if has_sr == has_cov or (given(scales) != given(rotations)):
         raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
     vb = settings if isinstance(settings, ViewBatch) else ViewBatch(settings)
-    if _wants_grad(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp):
+    cam_grad = vb.wants_grad()
+    if cam_grad or _wants_grad(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp):
         if means3D.dim() != 2 or means3D.shape[1] != 3:
             raise RuntimeError("means3D must have dimensions (num_points, 3)")
         if means2D is not None:
@@ -425,7 +489,8 @@ def rasterize_views(settings, means3D, opacities, shs=None,
                 _dev_f32_grad(opacities, dev), _dev_f32_grad(shs, dev) if given(shs) else None,
                 _dev_f32_grad(colors_precomp, dev) if given(colors_precomp) else None,
                 _dev_f32_grad(scales, dev) if has_sr else None, _dev_f32_grad(rotations, dev) if has_sr else None,
-                _dev_f32_grad(cov3D_precomp, dev) if has_cov else None)
+                _dev_f32_grad(cov3D_precomp, dev) if has_cov else None,
+                *(vb.camera_inputs(dev) if cam_grad else ()))
         finally:
             if home != dev.index:
                 torch.cuda.set_device(home)

@@ -301,6 +301,32 @@ int gr_raster_backward_aux(int64_t P, int M, const float* means3D, const float* 
                            int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
                            float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D, void* scratch,
                            size_t scratch_bytes, void* stream);
+/* Camera gradients: gr_raster_backward_aux that also writes the gradients with respect to the three camera tensors of
+ * every view, taken as three independent inputs (a caller that composes them from a pose chains through them):
+ *   dL_dviewmatrix (num_views, 16), dL_dprojmatrix (num_views, 16): element j * 4 + c is the derivative by the value the
+ *     kernels read as viewmatrix[j * 4 + c] / projmatrix[j * 4 + c] of gr_raster_view; column 3 of viewmatrix and column 2
+ *     of projmatrix are never read by the forward: zeros
+ *   dL_dcampos (num_views, 3): through the SH view direction only; zeros with colors_precomp
+ * Each may be NULL (not written); with all three NULL the call is gr_raster_backward_aux.  tanfovx, tanfovy,
+ * scale_modifier and bg get no gradient.  Every other output is bit-identical to gr_raster_backward_aux's (with
+ * GR_RASTER_BWD_COLOR_ONLY: to gr_raster_backward's).  Summed per view over the Gaussians in a fixed order, no atomics:
+ * bitwise reproducible, and a view's result does not depend on the other views of the call.
+ * GR_RASTER_BWD_COLOR_ONLY in `flags`: the forward was gr_raster_render_keep; dL_ddepth and dL_dalpha must be NULL and the
+ * slots hold gr_raster_backward's nine floats.
+ * scratch: gr_raster_backward_cam_bytes(..., flags) bytes, `flags` as in the call: gr_raster_backward_aux_bytes (with
+ * GR_RASTER_BWD_COLOR_ONLY: gr_raster_backward_bytes) plus 27 floats per view and 256 Gaussians. */
+#define GR_RASTER_BWD_COLOR_ONLY 8
+size_t gr_raster_backward_cam_bytes(int64_t P, int num_views, int width, int height, const int64_t* h_num_rendered,
+                                    int flags);
+int gr_raster_backward_cam(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
+                           const float* opacities, const float* scales, const float* rotations, const float* cov3D_precomp,
+                           const gr_raster_view* h_views, int num_views, const void* geom, size_t geom_bytes,
+                           const void* bin, size_t bin_bytes, const int64_t* h_num_rendered, const float* final_T,
+                           const int32_t* n_contrib, const float* dL_dcolor, const float* dL_ddepth, const float* dL_dalpha,
+                           int flags, float* dL_dmeans3D, float* dL_dmeans2D, float* dL_dshs, float* dL_dcolors,
+                           float* dL_dopacity, float* dL_dscales, float* dL_drotations, float* dL_dcov3D,
+                           float* dL_dviewmatrix /* (V,16) */, float* dL_dprojmatrix /* (V,16) */,
+                           float* dL_dcampos /* (V,3) */, void* scratch, size_t scratch_bytes, void* stream);
 /* present[i] = 1 iff Gaussian i passes the near-plane test of `viewmatrix` (markVisible). */
 int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewmatrix,
                            uint8_t* present, void* stream);
