@@ -382,7 +382,10 @@ extern "C" int gr_lgr_register_verify(const float* ref_corr_points, const float*
                                       int correspondence_threshold, int num_refinement_steps, float* out_transform,
                                       void* ws, size_t ws_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  GR_REQUIRE(num_corr >= 0 && batch >= 0 && num_refinement_steps >= 1 && num_corr < (1ll << 31), "bad arguments");
+  GR_REQUIRE(num_corr >= 0 && batch >= 0 && num_refinement_steps >= 0 && num_corr < (1ll << 31), "bad arguments");
+  // the fit on the best hypothesis' mask is unconditional in the reference (:187), only the loop behind it counts steps
+  // (:188 range(steps - 1)): 0 steps give what 1 step gives
+  if (num_refinement_steps < 1) num_refinement_steps = 1;
   GR_REQUIRE(out_transform != nullptr, "out_transform is null");
   GR_REQUIRE(num_corr > 0, "no correspondences: the reference's procrustes would divide by eps here");
   GR_REQUIRE(ref_corr_points && src_corr_points && corr_scores && pm_ws, "null argument");
@@ -436,8 +439,9 @@ extern "C" int gr_lgr_register_seg(const float* ref_corr_points, const float* sr
                                    int num_refinement_steps, float* out_transforms, int32_t* out_seg_rows, void* ws,
                                    size_t ws_bytes, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  GR_REQUIRE(num_corr >= 0 && batch >= 0 && nseg >= 0 && num_refinement_steps >= 1 && num_corr < (1ll << 31) &&
+  GR_REQUIRE(num_corr >= 0 && batch >= 0 && nseg >= 0 && num_refinement_steps >= 0 && num_corr < (1ll << 31) &&
              nseg < (1 << 24), "bad arguments");
+  if (num_refinement_steps < 1) num_refinement_steps = 1;  // as in gr_lgr_register_verify
   if (nseg == 0) return GR_OK;
   GR_REQUIRE(out_transforms && pm_ws && seg_patch_off, "null argument");
   GR_REQUIRE(num_corr == 0 || (ref_corr_points && src_corr_points && corr_scores), "null argument");

@@ -387,7 +387,7 @@ __global__ __launch_bounds__(1024) void ransac_best_kernel(const float* __restri
   }
   if (threadIdx.x == 0 && out_stats) {
     out_stats[0] = s_cnt[0];
-    out_stats[1] = best;
+    out_stats[1] = s_cnt[0] >= 0 ? best : -1;  // no valid hypothesis: {-1, -1}, like a pair too short to sample
   }
 }
 

@@ -476,11 +476,14 @@ int gr_corr_gather(const float* score_mat, int64_t batch, int64_t k1, int64_t k2
  * (local_to_global_registration, correspondence_limit = None) + registration/procrustes.py:6-82, with no
  * host round trip.  Inputs are the outputs of gr_corr_gather (num_corr rows, torch.nonzero order) and `pm_ws`,
  * the workspace gr_corr_matrix / gr_corr_gather used (it holds the per-patch counts / offsets).
- * out_transform: 16 floats, row-major 4x4, on the device. */
+ * out_transform: 16 floats, row-major 4x4, on the device.
+ * All three entry points (gr_lgr_register, gr_lgr_register_verify, gr_lgr_register_seg): num_refinement_steps = 0 gives
+ * what 1 gives -- the first fit of :187 is unconditional, only the loop behind it (:188) counts steps. */
 size_t gr_lgr_workspace_bytes(int64_t batch);
 /* gr_lgr_register_verify: the same with a separate verification set (correspondence_limit is not None,
  * local_global_registration.py:145-152): hypotheses are fitted on all correspondences of each patch, scored and
- * refined on the `num_verify` rows of verify_* (the top-`correspondence_limit` global scores). */
+ * refined on the `num_verify` rows of verify_* (the top-`correspondence_limit` global scores).
+ * num_refinement_steps = 0 is accepted and gives what 1 gives (see gr_lgr_register). */
 int gr_lgr_register_verify(const float* ref_corr_points, const float* src_corr_points, const float* corr_scores,
                            int64_t num_corr, int64_t batch, const void* pm_ws, const float* verify_ref_points,
                            const float* verify_src_points, const float* verify_scores, int64_t num_verify,
@@ -493,7 +496,8 @@ int gr_lgr_register(const float* ref_corr_points, const float* src_corr_points, 
 /* Stack mode over `nseg` scene pairs: the `batch` patches (gr_corr_matrix / gr_corr_gather over ALL patches of the batch)
  * belong to pairs, pair s owning patches [seg_patch_off[s], seg_patch_off[s+1]) (DEVICE int32, nseg + 1 entries).
  * out_transforms: nseg x 16 floats on the device; out_seg_rows (optional, device int32[nseg + 1]): first correspondence row
- * of every pair, last entry = num_corr.  A pair without correspondences gets the identity.  Three launches, no host
+ * of every pair, last entry = num_corr.  A pair without correspondences gets the identity.  num_refinement_steps = 0 is
+ * accepted and gives what 1 gives (see gr_lgr_register).  Three launches, no host
  * synchronisation. */
 int gr_lgr_register_seg(const float* ref_corr_points, const float* src_corr_points, const float* corr_scores,
                         int64_t num_corr, int64_t batch, const void* pm_ws, const int32_t* seg_patch_off, int64_t nseg,
@@ -504,6 +508,9 @@ int gr_lgr_register_seg(const float* ref_corr_points, const float* src_corr_poin
  * TransformationEstimationPointToPoint(with_scaling)), called from model.py:209-215.  Row i of src_points
  * corresponds to row i of ref_points.  out_transform: 16 floats (4x4 row-major, scale folded into the 3x3
  * block) on the device; out_stats (optional, device int32[2]) = {inliers of the best hypothesis, its id}.
+ * Best = most inliers, then smallest sum of squared inlier residuals, then lowest id.  A sample without spread, or whose
+ * scale is not positive, is invalid (with_scaling only); when every hypothesis is invalid out_transform is the identity
+ * and out_stats = {-1, -1}.  ransac_n outside [3, 8] or num_corr < ransac_n: GR_ERR_INVALID, nothing is launched.
  * gr_ransac_sample_hash exposes the counter hash the sampler uses (index = hash % num_corr, retried with
  * attempt+1 on duplicates) so a checker can replay the same hypotheses. */
 uint32_t gr_ransac_sample_hash(uint32_t seed, uint32_t hypothesis, uint32_t k, uint32_t attempt);
