@@ -476,15 +476,16 @@ extern "C" int gr_geo_embedding(const float* points, int64_t n, const float* w_d
     set_error("geo_embedding workspace too small");
     return GR_ERR_WORKSPACE;
   }
+  const bool fp32_mfma = (reduction_mean & 2) != 0 || c > GE_SPLIT_CMAX || c % 16 != 0;
+  const int mean = reduction_mean & 1;
+  // every refusal comes before the first launch
+  GR_REQUIRE(!fp32_mfma || c % GE_K == 0, "geo_embedding: the fp32-MFMA kernel needs hidden_dim %% 32 == 0 (got %lld)", (long long)c);
   Carver cv(ws);
   int32_t* knn = cv.take<int32_t>((size_t)n * std::max<int64_t>(angle_k, 1));
   if (angle_k > 0)
     hipLaunchKernelGGL(geo_knn_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, points, (int)n, (int)angle_k, knn);
-  const bool fp32_mfma = (reduction_mean & 2) != 0 || c > GE_SPLIT_CMAX || c % 16 != 0;
-  const int mean = reduction_mean & 1;
   const dim3 grid((unsigned)((n * n + GE_ROWS - 1) / GE_ROWS), (unsigned)((c + GE_COLS - 1) / GE_COLS));
   if (fp32_mfma) {
-    GR_REQUIRE(c % GE_K == 0, "geo_embedding: the fp32-MFMA kernel needs hidden_dim %% 32 == 0 (got %lld)", (long long)c);
     KernelTimer timer("geo_embedding", stream);
     hipLaunchKernelGGL(geo_embedding_kernel, grid, dim3(GE_T), 0, stream, points, (int)n, knn, (int)angle_k, w_d, b_d,
                        w_a, b_a, div_term, (int)c, sigma_d, factor_a, mean, out);

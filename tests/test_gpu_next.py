@@ -1,5 +1,6 @@
 """GPU parity for the "next" rows: fused Sinkhorn and KPConv forward vs golden vectors
-from the reference's own modules, and vs the NumPy oracle at demo shapes."""
+from the reference's own modules, and vs the NumPy oracle at demo shapes.  The geometric structure embedding is held to
+float64 over the whole tensor, diagonal included, in tests/test_gpu_geo_embedding_f64.py."""
 import numpy as np
 import pytest
 import torch
