@@ -11,6 +11,10 @@ the truth perturbed by a small rotation, translation and scale.  The fixed scene
 under the true transform (colour and depth: what scene A would show); Adam then runs on a 7-parameter correction
 (rotation vector, translation, log scale) of the coarse estimate with an L1 colour + depth loss through
 rasterize_views(..., render_depth=True).  Prints the transform error before and after.
+
+`--loss dssim` replaces the L1 colour term by the 3DGS photometric loss, 0.8 L1 + 0.2 (1 - SSIM)
+(gaussreg_amd.image_loss.photometric_loss), weighted per pixel by the alpha map of the target render: where the fixed
+scene shows nothing, the colours are not compared.
 """
 import argparse
 import math
@@ -22,6 +26,7 @@ import torch
 sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")))
 
 from gaussreg_amd import pose, synthetic  # noqa: E402
+from gaussreg_amd.image_loss import photometric_loss  # noqa: E402
 from gaussreg_amd.rasterizer import GaussianRasterizationSettings, rasterize_views  # noqa: E402
 
 
@@ -38,6 +43,8 @@ def main():
     ap.add_argument("--steps", type=int, default=150)
     ap.add_argument("--width", type=int, default=320)
     ap.add_argument("--height", type=int, default=240)
+    ap.add_argument("--loss", choices=("l1", "dssim"), default="l1",
+                    help="colour term: plain L1, or the alpha-weighted L1 + D-SSIM photometric loss")
     args = ap.parse_args()
     if not args.synthetic:
         ap.error("only --synthetic is implemented: pass two registered scenes through the library calls shown here")
@@ -56,9 +63,9 @@ def main():
             vm2, pm2, cp2, factor = pose.similarity_camera(vm, s, R, t, projmatrix=pm)
             sets.append(GaussianRasterizationSettings(H, W, c["tanfovx"], c["tanfovy"], bg, 1.0, vm2, pm2, 3, cp2, False,
                                                       False))
-        color, _, _, depth, _ = rasterize_views(sets, scene["means3D"], scene["opacities"], shs=scene["shs"],
+        color, _, _, depth, alpha = rasterize_views(sets, scene["means3D"], scene["opacities"], shs=scene["shs"],
                                                 scales=scene["scales"], rotations=scene["rotations"], render_depth=True)
-        return color, depth * factor
+        return color, depth * factor, alpha
 
     # the known transform and a coarse estimate of it
     s_true = torch.tensor(1.1, device=dev)
@@ -68,7 +75,8 @@ def main():
     t0 = t_true + torch.tensor([0.03, -0.02, 0.02], device=dev)
     s0 = s_true * 1.02
     with torch.no_grad():
-        target_c, target_d = render(s_true, R_true, t_true)
+        target_c, target_d, target_alpha = render(s_true, R_true, t_true)
+    target_alpha = target_alpha[:, 0].contiguous()
 
     w = torch.zeros(3, device=dev, requires_grad=True)
     dt = torch.zeros(3, device=dev, requires_grad=True)
@@ -87,8 +95,12 @@ def main():
     opt = torch.optim.Adam([w, dt, ls], lr=2e-3)
     for step in range(args.steps):
         opt.zero_grad()
-        c, d = render(*current())
-        loss = (c - target_c).abs().mean() + 0.1 * (d - target_d).abs().mean()
+        c, d, _ = render(*current())
+        if args.loss == "dssim":
+            colour = photometric_loss(c, target_c, 0.2, weight=target_alpha)
+        else:
+            colour = (c - target_c).abs().mean()
+        loss = colour + 0.1 * (d - target_d).abs().mean()
         loss.backward()
         opt.step()
         if step % 25 == 0 or step == args.steps - 1:

@@ -158,6 +158,16 @@ SIGNATURES.update({
 })
 
 
+SIGNATURES.update({
+    "gr_image_loss_workspace_bytes": (c_size, [c_int] * 4),
+    "gr_image_loss_keep_bytes": (c_size, [c_int] * 4),
+    "gr_image_loss_forward": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_f32, c_void, c_void, c_void, c_size,
+                                      c_void, c_size, c_void]),
+    "gr_image_loss_backward": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_f32, c_void, c_size, c_void, c_void,
+                                       c_void, c_void, c_size, c_void]),
+})
+
+
 class HipLibraryError(RuntimeError):
     pass
 

@@ -595,6 +595,35 @@ int gr_fps_debug_force_fallback(int mode);
 int gr_fps_debug_bucket_sort(int on);
 
 /* ------------------------------------------------------------------------------------------------
+ * Photometric image loss of Gaussian-splatting training (the public 3DGS loss_utils formulas; nothing in the reference
+ * tree implements them): per view  loss_v = (1 - lambda) l1 + lambda (1 - ssim_mean).
+ * image, target: (V, C, H, W) fp32, C in {1, 3}, V * C <= 65535; weight: (V, H, W) fp32, >= 0 (not checked), or NULL = ones.
+ *   SSIM per pixel and channel with the 11 x 11 Gaussian window (sigma 1.5, fp32 taps normalised in double), applied
+ *   separably with zero padding 5, C1 = 0.01^2, C2 = 0.03^2, sigma_x^2 = E[xx] - mu_x^2 (and so on).
+ *   S = sum_p w_p;  l1 = sum_{c,p} w_p |x - y| / (C S);  ssim_mean = sum_{c,p} w_p ssim / (C S).
+ *   The weight scales the SSIM map and the L1 term only: the windows read every pixel.  A view with S = 0 has loss 0,
+ *   terms (0, 0, 0) and a gradient of exact zeros.
+ * gr_image_loss_forward: out_loss (V); out_terms (V, 3) = {l1, ssim_mean, S} per view, or NULL; keep = NULL (no backward
+ *   will follow) or gr_image_loss_keep_bytes() of device memory that receives three (V, C, H, W) maps, w d ssim / d mu_x,
+ *   w d ssim / d sigma_x^2, w d ssim / d sigma_xy; out_loss has the same bits with and without it.  workspace:
+ *   gr_image_loss_workspace_bytes() (one {sum w |x - y|, sum w ssim, sum w} slot per 32 x 16 tile and plane, added per view
+ *   in a fixed order by a second launch).
+ * gr_image_loss_backward: dL_dimage (V, C, H, W) = dL_dloss[v] * d loss_v / d image, the gradient to `image` alone (target
+ *   and weight are constants; sign(0) = 0 in the L1 term).  image, target, weight, lambda_dssim, keep and out_terms as in
+ *   (as written by) the forward call; workspace is not used and may be NULL.
+ * Both are asynchronous on `stream` without any host synchronisation, use no atomics, are bitwise reproducible, and a
+ * view's result does not depend on the other views of the call.  Errors: GR_ERR_INVALID (shape, lambda outside [0, 1],
+ * null pointer), GR_ERR_WORKSPACE (workspace or keep too small); the size queries return 0 for an invalid shape. */
+size_t gr_image_loss_workspace_bytes(int V, int C, int H, int W);
+size_t gr_image_loss_keep_bytes(int V, int C, int H, int W);
+int gr_image_loss_forward(const float* image, const float* target, const float* weight, int V, int C, int H, int W,
+                          float lambda_dssim, float* out_loss, float* out_terms, void* keep, size_t keep_bytes,
+                          void* workspace, size_t workspace_bytes, void* stream);
+int gr_image_loss_backward(const float* image, const float* target, const float* weight, int V, int C, int H, int W,
+                           float lambda_dssim, const void* keep, size_t keep_bytes, const float* out_terms,
+                           const float* dL_dloss, float* dL_dimage, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Harness support, NOT a reference interface: stand-in position descriptors of the configs[4] pair pipeline
  * (gaussreg_amd/pair_pipeline.py; the learned features are not available offline).  out (n, c) =
  * mask * scale * cos((T[transform_id] p) W + b), rows optionally L2-normalised; transforms (k, 3, 4) row-major or NULL,
