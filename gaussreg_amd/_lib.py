@@ -168,6 +168,21 @@ SIGNATURES.update({
 })
 
 
+class GsAdamGroup(ctypes.Structure):
+    """struct gr_gs_adam_group (include/gaussreg_hip.h)."""
+    _fields_ = [("param", c_void), ("grad", c_void), ("exp_avg", c_void), ("exp_avg_sq", c_void),
+                ("lr", ctypes.c_double), ("K", ctypes.c_int32)]
+
+
+GS_ADAM_MAX_GROUPS = 8
+
+SIGNATURES.update({
+    "gr_gs_adam_step": (c_int, [ctypes.POINTER(GsAdamGroup), c_int, c_i64] + [ctypes.c_double] * 5 + [c_void, c_void, c_int,
+                                                                                                    c_void]),
+    "gr_gs_densify_stats": (c_int, [c_void, c_void, c_i64, c_int, c_void, c_void, c_void, c_void]),
+})
+
+
 class HipLibraryError(RuntimeError):
     pass
 
