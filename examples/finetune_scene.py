@@ -10,7 +10,9 @@ is then perturbed (DC colours, logit opacities, log scales) and fitted back to t
     DensifyStats.update(means2D.grad, radii)  # what a densify / prune step would read
 
 The raw parameters, their activations (in torch) and the learning rates are upstream 3DGS's: `xyz`, `f_dc`, `f_rest`,
-logit `opacity`, log `scaling`, unnormalised `rotation`.  `--optimizer torch` runs the same loop on torch.optim.Adam
+logit `opacity`, log `scaling`, unnormalised `rotation`.  `--densify-every N` (off by default) runs
+gaussreg_amd.scene_densify.densify_and_prune on those statistics every N steps until `--densify-until`, with upstream's
+thresholds, and `--opacity-reset-every M` its reset_opacity; the loop then goes on with the returned tensors.  `--optimizer torch` runs the same loop on torch.optim.Adam
 (dense: every Gaussian moves every step), for comparison.  Prints the loss and the PSNR over all views before and after.
 """
 import argparse
@@ -26,6 +28,7 @@ sys.path.insert(0, os.path.abspath(os.path.join(os.path.dirname(__file__), "..")
 from gaussreg_amd import synthetic  # noqa: E402
 from gaussreg_amd.image_loss import photometric_loss  # noqa: E402
 from gaussreg_amd.rasterizer import GaussianRasterizationSettings, ViewBatch, rasterize_views  # noqa: E402
+from gaussreg_amd.scene_densify import densify_and_prune, reset_opacity  # noqa: E402
 from gaussreg_amd.scene_optim import DensifyStats, GaussianAdam  # noqa: E402
 
 # upstream 3DGS arguments/__init__.py (position_lr_init without the scene-extent factor, feature_lr, feature_lr / 20, ...)
@@ -46,9 +49,13 @@ def render(raw, views, means2D=None):
                            means2D=means2D)[:2]
 
 
-def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer="hip", seed=0, log=None):
+def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer="hip", seed=0, log=None, densify_every=0,
+             densify_until=None, opacity_reset_every=0, densify_grad_threshold=2e-4, min_opacity=5e-3, percent_dense=0.01,
+             max_screen_size=None):
     """-> dict: loss / psnr before and after over all views, the raw parameters at the start and at the end, the per-step
-    visibility (steps, P) bool, and the DensifyStats."""
+    visibility (steps, P) bool, and the DensifyStats.  With densify_every > 0 (GaussianAdam only) the Gaussian count
+    changes: instead of the per-step visibility the dict holds `densifications` (step, P_old, P_new, counts per event),
+    `counts` (the Gaussian count after each event), `raw` (the live tensors by name) and `one_view` (the view batches)."""
     dev = torch.device("cuda")
     raw = raw_parameters(synthetic.gaussians_c2(points, seed, SH_DEGREE), dev)
     bg = torch.zeros(3, device=dev)
@@ -81,7 +88,14 @@ def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer
     stats = DensifyStats(points, dev)
     start = {name: p.detach().clone() for name, p in raw.items()}
     before = evaluate()
-    seen = torch.zeros((steps, points), dtype=torch.bool, device=dev)
+    densify = densify_every > 0
+    if densify and optimizer != "hip":
+        raise ValueError("densification runs on GaussianAdam (--optimizer hip)")
+    if densify:
+        extent = (raw["xyz"].detach() - raw["xyz"].detach().mean(0)).norm(dim=1).max().item() * 1.1  # the scene's radius, for upstream's cameras_extent
+        noise_gen = torch.Generator(device=dev).manual_seed(seed + 2)
+    events, counts = [], []
+    seen = None if densify else torch.zeros((steps, points), dtype=torch.bool, device=dev)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for step in range(steps):
@@ -96,14 +110,33 @@ def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer
             opt.step()
         stats.update(means2D.grad, radii)
         opt.zero_grad(set_to_none=True)
-        seen[step] = radii[0] > 0
+        if not densify:
+            seen[step] = radii[0] > 0
         if log and (step % 50 == 0 or step == steps - 1):
-            log(f"  step {step:4d}  view {v}  loss {loss.item():.6f}  visible {int(seen[step].sum())} / {points}")
+            log(f"  step {step:4d}  view {v}  loss {loss.item():.6f}  visible {int((radii[0] > 0).sum())} / {points}")
+        done = step + 1
+        if densify and done % densify_every == 0 and done < steps and (densify_until is None or done <= densify_until):
+            r = densify_and_prune(opt, stats, densify_grad_threshold, min_opacity, extent, max_screen_size=max_screen_size,
+                                  percent_dense=percent_dense, generator=noise_gen)
+            for name in raw:  # the loop goes on with the tensors the optimiser now holds
+                raw[name] = r.tensors[name]
+            events.append({"step": done, "P_old": points, "P_new": r.P_new, "counts": r.counts})
+            counts.append(r.P_new)
+            if log:
+                log(f"  step {done:4d}  densified: {points} -> {r.P_new} Gaussians (kept {r.counts[0]}, cloned {r.counts[1]}, "
+                    f"split {r.counts[2]})")
+            points = r.P_new
+        if densify and opacity_reset_every > 0 and done % opacity_reset_every == 0 and done < steps:
+            reset_opacity(opt)
     torch.cuda.synchronize()
     seconds = time.perf_counter() - t0
     after = evaluate()
-    return {"before": before, "after": after, "start": start, "end": {name: p.detach() for name, p in raw.items()}, "seen": seen,
-            "stats": stats, "optimizer": opt, "seconds": seconds}
+    out = {"before": before, "after": after, "start": start, "end": {name: p.detach() for name, p in raw.items()}, "seen": seen,
+           "stats": stats, "optimizer": opt, "seconds": seconds}
+    if densify:
+        del out["seen"]
+        out.update(densifications=events, counts=counts, raw=raw, one_view=one_view)
+    return out
 
 
 def main():
@@ -116,15 +149,25 @@ def main():
     ap.add_argument("--height", type=int, default=240)
     ap.add_argument("--optimizer", choices=("hip", "torch"), default="hip",
                     help="GaussianAdam with the view's radii as visibility, or torch.optim.Adam over every Gaussian")
+    ap.add_argument("--densify-every", type=int, default=0, help="densify and prune every N steps (0: never; hip optimizer)")
+    ap.add_argument("--densify-until", type=int, default=None, help="last step at which to densify (default: no limit)")
+    ap.add_argument("--opacity-reset-every", type=int, default=0, help="reset the opacities every M steps (0: never)")
+    ap.add_argument("--densify-grad-threshold", type=float, default=2e-4, help="upstream's densify_grad_threshold")
+    ap.add_argument("--min-opacity", type=float, default=5e-3, help="prune below this opacity")
+    ap.add_argument("--percent-dense", type=float, default=0.01, help="clone / split boundary as a fraction of the extent")
+    ap.add_argument("--max-screen-size", type=float, default=None, help="prune above this screen radius (and 0.1 x extent)")
     args = ap.parse_args()
     if not args.synthetic:
         ap.error("only --synthetic is implemented: load a scene with gaussreg_amd.gs_io and follow finetune()")
-    r = finetune(args.points, args.views, args.steps, args.width, args.height, args.optimizer, log=print)
+    r = finetune(args.points, args.views, args.steps, args.width, args.height, args.optimizer, log=print,
+                 densify_every=args.densify_every, densify_until=args.densify_until, opacity_reset_every=args.opacity_reset_every,
+                 densify_grad_threshold=args.densify_grad_threshold, min_opacity=args.min_opacity,
+                 percent_dense=args.percent_dense, max_screen_size=args.max_screen_size)
     print(f"before: loss {r['before'][0]:.6f}  PSNR {r['before'][1]:.2f} dB")
     print(f"after:  loss {r['after'][0]:.6f}  PSNR {r['after'][1]:.2f} dB   ({args.steps} steps, {args.optimizer} Adam, "
           f"{1e3 * r['seconds'] / max(args.steps, 1):.2f} ms per step)")
     st = r["stats"]
-    print(f"densification statistics: {int((st.denom > 0).sum())} of {args.points} Gaussians seen, "
+    print(f"densification statistics: {int((st.denom > 0).sum())} of {st.denom.shape[0]} Gaussians seen, "
           f"largest mean screen-space gradient {st.mean_grad().max().item():.3e}, largest radius {int(st.max_radii.max())}")
 
 

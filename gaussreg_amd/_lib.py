@@ -183,6 +183,22 @@ SIGNATURES.update({
 })
 
 
+class GsDensifyGroup(ctypes.Structure):
+    """struct gr_gs_densify_group (include/gaussreg_hip.h)."""
+    _fields_ = [("src_param", c_void), ("dst_param", c_void), ("src_exp_avg", c_void), ("dst_exp_avg", c_void),
+                ("src_exp_avg_sq", c_void), ("dst_exp_avg_sq", c_void), ("K", ctypes.c_int32), ("role", ctypes.c_int32)]
+
+
+GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = 0, 1, 2
+
+SIGNATURES.update({
+    "gr_gs_densify_plan_workspace_bytes": (c_size, [c_i64]),
+    "gr_gs_densify_plan": (c_int, [c_void] * 5 + [c_i64] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double, c_void, c_void, c_void,
+                                                                                     c_i64p, c_void, c_size, c_void]),
+    "gr_gs_densify_apply": (c_int, [ctypes.POINTER(GsDensifyGroup), c_int, c_i64, c_i64] + [c_void] * 6),
+})
+
+
 class HipLibraryError(RuntimeError):
     pass
 

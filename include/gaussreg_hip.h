@@ -656,6 +656,45 @@ int gr_gs_densify_stats(const float* means2D_grad, const int32_t* radii, int64_t
                         int32_t* denom, int32_t* max_radii, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Densification of a Gaussian scene: upstream 3DGS's densify_and_prune with two children per split (the
+ * definition is in INTEGRATION.md).
+ * gr_gs_densify_plan: classifies the P Gaussians in fp32 from scaling (P, 3) logs, opacity (P) logits and the three
+ *   statistics, and writes the gather plan of the new scene: source[row] = the Gaussian row `row` comes from, kind[row] =
+ *   0 original, 1 clone, 2 / 3 child 0 / 1, in the order [originals kept][clones][children 0][children 1], each block in
+ *   ascending source; counts (DEVICE, 4 int32) = the four block lengths, their sum is P_new <= 2 P.  source and kind hold
+ *   2 P entries.  use_max_screen_size = 0: no radius and no world-size pruning.  h_counts (HOST, 4, may be NULL): the same
+ *   counts, copied back -- with it the call synchronises `stream` (the only host synchronisation of a densification),
+ *   without it the call is asynchronous.  Three launches, no atomics, bitwise reproducible.  P <= 2^30.
+ *   `ws`: gr_gs_densify_plan_workspace_bytes(P) (host only; 0 for P outside [1, 2^30]).
+ * gr_gs_densify_apply: ONE launch gathers the parameter and both moments of up to GR_GS_ADAM_MAX_GROUPS groups into new
+ *   tensors of P_new rows: dst[row] = src[source[row]] bit for bit, except that moments of rows with kind != 0 are zeros and
+ *   that, in rows with kind >= 2, the GR_GS_DENSIFY_SCALING group receives log(exp(scaling) / 1.6) and the GR_GS_DENSIFY_XYZ
+ *   group xyz + R(q / |q|) (exp(scaling) o noise[source][kind - 2]), q = rotation in (r, x, y, z) order.  scaling (P, 3),
+ *   rotation (P, 4) are the OLD tensors, noise is (P, 2, 3); all three may be NULL when no group has the xyz role.  A group
+ *   without state has all four moment pointers NULL.  `groups` is a HOST array.  P_new = 0 or K = 0 launches nothing.
+ *   Asynchronous, no atomics, no workspace. */
+#define GR_GS_DENSIFY_CARRIED 0
+#define GR_GS_DENSIFY_XYZ 1
+#define GR_GS_DENSIFY_SCALING 2
+typedef struct gr_gs_densify_group {
+  const float* src_param;
+  float* dst_param;
+  const float* src_exp_avg;
+  float* dst_exp_avg;
+  const float* src_exp_avg_sq;
+  float* dst_exp_avg_sq;
+  int32_t K;    /* floats per Gaussian; 0: the group is skipped */
+  int32_t role; /* GR_GS_DENSIFY_* */
+} gr_gs_densify_group;
+size_t gr_gs_densify_plan_workspace_bytes(int64_t P);
+int gr_gs_densify_plan(const float* scaling, const float* opacity, const float* grad_accum, const int32_t* denom,
+                       const int32_t* max_radii, int64_t P, double max_grad, double min_opacity, double extent,
+                       double percent_dense, int use_max_screen_size, double max_screen_size, int32_t* source,
+                       uint8_t* kind, int32_t* counts, int64_t* h_counts, void* ws, size_t ws_bytes, void* stream);
+int gr_gs_densify_apply(const gr_gs_densify_group* groups, int n_groups, int64_t P, int64_t P_new, const int32_t* source,
+                        const uint8_t* kind, const float* scaling, const float* rotation, const float* noise, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Harness support, NOT a reference interface: stand-in position descriptors of the configs[4] pair pipeline
  * (gaussreg_amd/pair_pipeline.py; the learned features are not available offline).  out (n, c) =
  * mask * scale * cos((T[transform_id] p) W + b), rows optionally L2-normalised; transforms (k, 3, 4) row-major or NULL,
