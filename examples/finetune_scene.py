@@ -1,6 +1,7 @@
 """Fine-tune a Gaussian-splatting scene on images: the 3DGS training step on this library's kernels.
 
     python examples/finetune_scene.py --synthetic [--optimizer torch]
+    python examples/finetune_scene.py --synthetic --from-points 5000
 
 `--synthetic` (needs no data): the synthetic C2 scene is the truth and is rendered once from a ring of cameras.  The scene
 is then perturbed (DC colours, logit opacities, log scales) and fitted back to those images, one view per step:
@@ -14,6 +15,11 @@ logit `opacity`, log `scaling`, unnormalised `rotation`.  `--densify-every N` (o
 gaussreg_amd.scene_densify.densify_and_prune on those statistics every N steps until `--densify-until`, with upstream's
 thresholds, and `--opacity-reset-every M` its reset_opacity; the loop then goes on with the returned tensors.  `--optimizer torch` runs the same loop on torch.optim.Adam
 (dense: every Gaussian moves every step), for comparison.  Prints the loss and the PSNR over all views before and after.
+
+`--from-points M` trains from a point cloud instead of a perturbed scene: M of the truth's means (a seeded subset) with
+their DC colours as RGB play the SfM cloud, gaussreg_amd.scene_init.gaussians_from_points (upstream's create_from_pcd: the
+exact 3-nearest-neighbour kernel gives the initial scales) builds the scene, and the loop runs with densification on and
+upstream's exponential schedule (scene_init.expon_lr, times the scene's extent) on the `xyz` learning rate.
 """
 import argparse
 import math
@@ -29,11 +35,14 @@ from gaussreg_amd import synthetic  # noqa: E402
 from gaussreg_amd.image_loss import photometric_loss  # noqa: E402
 from gaussreg_amd.rasterizer import GaussianRasterizationSettings, ViewBatch, rasterize_views  # noqa: E402
 from gaussreg_amd.scene_densify import densify_and_prune, reset_opacity  # noqa: E402
+from gaussreg_amd.scene_init import SH_C0, expon_lr, gaussians_from_points  # noqa: E402
 from gaussreg_amd.scene_optim import DensifyStats, GaussianAdam  # noqa: E402
 
 # upstream 3DGS arguments/__init__.py (position_lr_init without the scene-extent factor, feature_lr, feature_lr / 20, ...)
 LEARNING_RATES = {"xyz": 1.6e-4, "f_dc": 2.5e-3, "f_rest": 2.5e-3 / 20.0, "opacity": 5e-2, "scaling": 5e-3, "rotation": 1e-3}
 SH_DEGREE = 3
+# upstream's position_lr_init / _final / _delay_mult / _max_steps, for --from-points
+POSITION_LR = dict(lr_init=1.6e-4, lr_final=1.6e-6, lr_delay_mult=0.01, max_steps=30_000)
 
 
 def raw_parameters(g, dev):
@@ -51,11 +60,13 @@ def render(raw, views, means2D=None):
 
 def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer="hip", seed=0, log=None, densify_every=0,
              densify_until=None, opacity_reset_every=0, densify_grad_threshold=2e-4, min_opacity=5e-3, percent_dense=0.01,
-             max_screen_size=None):
+             max_screen_size=None, from_points=0):
     """-> dict: loss / psnr before and after over all views, the raw parameters at the start and at the end, the per-step
     visibility (steps, P) bool, and the DensifyStats.  With densify_every > 0 (GaussianAdam only) the Gaussian count
     changes: instead of the per-step visibility the dict holds `densifications` (step, P_old, P_new, counts per event),
-    `counts` (the Gaussian count after each event), `raw` (the live tensors by name) and `one_view` (the view batches)."""
+    `counts` (the Gaussian count after each event), `raw` (the live tensors by name) and `one_view` (the view batches).
+    from_points = M > 0: start from gaussians_from_points on M of the truth's means instead of the perturbed truth, with
+    densification on (every `densify_every` steps, 100 if that is 0) and expon_lr on the xyz group."""
     dev = torch.device("cuda")
     raw = raw_parameters(synthetic.gaussians_c2(points, seed, SH_DEGREE), dev)
     bg = torch.zeros(3, device=dev)
@@ -67,10 +78,21 @@ def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer
     one_view = [ViewBatch([s]) for s in settings]
     with torch.no_grad():
         target = render(raw, all_views)[0]
-        gen = torch.Generator(device=dev).manual_seed(seed + 1)
-        raw["f_dc"] += 0.15 * torch.randn(raw["f_dc"].shape, generator=gen, device=dev)
-        raw["opacity"] += 0.5 * torch.randn(raw["opacity"].shape, generator=gen, device=dev)
-        raw["scaling"] += 0.1 * torch.randn(raw["scaling"].shape, generator=gen, device=dev)
+        if from_points:
+            if not 3 < from_points <= points:
+                raise ValueError(f"from_points = {from_points} outside (3, points = {points}]")
+            subset = torch.randperm(points, generator=torch.Generator().manual_seed(seed + 3))[:from_points].to(dev)
+            cloud = raw["xyz"][subset].contiguous()
+            colors = (raw["f_dc"][subset, 0] * SH_C0 + 0.5).clamp_(0.0, 1.0)
+        else:
+            gen = torch.Generator(device=dev).manual_seed(seed + 1)
+            raw["f_dc"] += 0.15 * torch.randn(raw["f_dc"].shape, generator=gen, device=dev)
+            raw["opacity"] += 0.5 * torch.randn(raw["opacity"].shape, generator=gen, device=dev)
+            raw["scaling"] += 0.1 * torch.randn(raw["scaling"].shape, generator=gen, device=dev)
+    if from_points:
+        raw = gaussians_from_points(cloud, colors, SH_DEGREE)
+        points = from_points
+        densify_every = densify_every or 100
     for p in raw.values():
         p.requires_grad_(True)
 
@@ -100,6 +122,8 @@ def finetune(points=20_000, views=4, steps=200, width=320, height=240, optimizer
     t0 = time.perf_counter()
     for step in range(steps):
         v = step % views
+        if from_points:
+            opt.param_groups[0]["lr"] = extent * expon_lr(step, **POSITION_LR)
         means2D = torch.zeros((1, points, 3), device=dev, requires_grad=True)
         image, radii = render(raw, one_view[v], means2D)
         loss = photometric_loss(image, target[v:v + 1], 0.2)
@@ -156,13 +180,15 @@ def main():
     ap.add_argument("--min-opacity", type=float, default=5e-3, help="prune below this opacity")
     ap.add_argument("--percent-dense", type=float, default=0.01, help="clone / split boundary as a fraction of the extent")
     ap.add_argument("--max-screen-size", type=float, default=None, help="prune above this screen radius (and 0.1 x extent)")
+    ap.add_argument("--from-points", type=int, default=0, metavar="M",
+                    help="start from a cloud of M of the truth's points (scene_init.gaussians_from_points), densification on")
     args = ap.parse_args()
     if not args.synthetic:
         ap.error("only --synthetic is implemented: load a scene with gaussreg_amd.gs_io and follow finetune()")
     r = finetune(args.points, args.views, args.steps, args.width, args.height, args.optimizer, log=print,
                  densify_every=args.densify_every, densify_until=args.densify_until, opacity_reset_every=args.opacity_reset_every,
                  densify_grad_threshold=args.densify_grad_threshold, min_opacity=args.min_opacity,
-                 percent_dense=args.percent_dense, max_screen_size=args.max_screen_size)
+                 percent_dense=args.percent_dense, max_screen_size=args.max_screen_size, from_points=args.from_points)
     print(f"before: loss {r['before'][0]:.6f}  PSNR {r['before'][1]:.2f} dB")
     print(f"after:  loss {r['after'][0]:.6f}  PSNR {r['after'][1]:.2f} dB   ({args.steps} steps, {args.optimizer} Adam, "
           f"{1e3 * r['seconds'] / max(args.steps, 1):.2f} ms per step)")

@@ -199,6 +199,14 @@ SIGNATURES.update({
 })
 
 
+GS_KNN_MAX_K = 8
+
+SIGNATURES.update({
+    "gr_gs_knn_workspace_bytes": (c_size, [c_i64, c_int]),
+    "gr_gs_knn": (c_int, [c_void, c_i64, c_int, c_void, c_void, c_void, c_void, c_size, c_void]),
+})
+
+
 class HipLibraryError(RuntimeError):
     pass
 

@@ -695,6 +695,22 @@ int gr_gs_densify_apply(const gr_gs_densify_group* groups, int n_groups, int64_t
                         const uint8_t* kind, const float* scaling, const float* rotation, const float* noise, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Scene initialisation from a point cloud: exact k nearest neighbours inside ONE cloud (what upstream
+ * 3DGS's create_from_pcd takes from simple_knn.distCUDA2).  points (n, 3) fp32.  The result is that of an exhaustive
+ * enumeration:  d(i, j) = ((dx*dx + dy*dy) + dz*dz) in fp32 with dx = p[j].x - p[i].x, three multiplies and two adds;
+ * the neighbours of i are the k points j != i (by index: a duplicate point is a neighbour at distance 0) smallest under
+ * the order (d, j).  Every output may be NULL:
+ *   dist2 (n, k) fp32 ascending;  index (n, k) int64;  mean (n) fp32 = (((d0 + d1) + ..) + d_{k-1}) / (float)k, an IEEE
+ *   division (k = 3: distCUDA2).
+ * 1 <= k <= GR_GS_KNN_MAX_K, k < n < 2^31.  A non-finite coordinate: GR_ERR_INVALID ("points must be finite"), and the
+ * outputs are not written.  The call synchronises `stream` once (the finiteness flag).  Integer atomics only; the bits do
+ * not depend on scheduling.  `ws`: gr_gs_knn_workspace_bytes(n, k) (host only; 0 for an invalid shape). */
+#define GR_GS_KNN_MAX_K 8
+size_t gr_gs_knn_workspace_bytes(int64_t n, int k);
+int gr_gs_knn(const float* points, int64_t n, int k, float* dist2, int64_t* index, float* mean, void* ws, size_t ws_bytes,
+              void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Harness support, NOT a reference interface: stand-in position descriptors of the configs[4] pair pipeline
  * (gaussreg_amd/pair_pipeline.py; the learned features are not available offline).  out (n, c) =
  * mask * scale * cos((T[transform_id] p) W + b), rows optionally L2-normalised; transforms (k, 3, 4) row-major or NULL,
