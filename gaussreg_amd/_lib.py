@@ -48,6 +48,15 @@ class RasterView(ctypes.Structure):
                 ("sh_degree", ctypes.c_int32), ("prefiltered", ctypes.c_int32), ("debug", ctypes.c_int32)]
 
 
+# The three backward entries share their argument list; the map gradients and the camera outputs are spliced in.
+_BWD_HEAD = ([c_i64, c_int] + [c_void] * 7 +                    # P, M, the seven inputs
+             [ctypes.POINTER(RasterView), c_int, c_void, c_size, c_void, c_size, c_i64p] +  # views, geom, bin, num_rendered
+             [c_void] * 3)                                      # final_T, n_contrib, dL_dcolor
+_BWD_MAPS = [c_void] * 2                                        # dL_ddepth, dL_dalpha
+_BWD_GRADS = [c_int] + [c_void] * 8                             # flags, the eight input gradients
+_BWD_CAMERA = [c_void] * 3                                      # dL_dviewmatrix, dL_dprojmatrix, dL_dcampos
+_BWD_TAIL = [c_void, c_size, c_void]                            # scratch, its size, stream
+
 SIGNATURES.update({
     "gr_raster_geom_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
     "gr_raster_bin_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
@@ -68,18 +77,13 @@ SIGNATURES.update({
     "gr_raster_render_keep": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
                                       c_void, c_int, c_void]),
     "gr_raster_backward_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
-    "gr_raster_backward": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size, c_void,
-                                   c_size, c_i64p, c_void, c_void, c_void, c_int] + [c_void] * 8 + [c_void, c_size, c_void]),
+    "gr_raster_backward": (c_int, _BWD_HEAD + _BWD_GRADS + _BWD_TAIL),
     "gr_raster_render_aux": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
                                      c_void, c_void, c_void, c_void, c_int, c_void]),
     "gr_raster_backward_aux_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
-    "gr_raster_backward_aux": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size,
-                                       c_void, c_size, c_i64p, c_void, c_void, c_void, c_void, c_void, c_int] +
-                               [c_void] * 8 + [c_void, c_size, c_void]),
+    "gr_raster_backward_aux": (c_int, _BWD_HEAD + _BWD_MAPS + _BWD_GRADS + _BWD_TAIL),
     "gr_raster_backward_cam_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p, c_int]),
-    "gr_raster_backward_cam": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_size,
-                                       c_void, c_size, c_i64p, c_void, c_void, c_void, c_void, c_void, c_int] +
-                               [c_void] * 11 + [c_void, c_size, c_void]),
+    "gr_raster_backward_cam": (c_int, _BWD_HEAD + _BWD_MAPS + _BWD_GRADS + _BWD_CAMERA + _BWD_TAIL),
 })
 
 

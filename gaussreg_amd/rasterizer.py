@@ -1,4 +1,4 @@
-"""Mirror of ``diff_gaussian_rasterization`` (forward only) on the HIP rasterizer.
+"""Mirror of ``diff_gaussian_rasterization`` (forward and backward) on the HIP rasterizer.
 
 The package is NOT part of the GaussReg tree; the API below is the public
 upstream one (graphdeco-inria/diff-gaussian-rasterization, diff_gaussian_rasterization/__init__.py):
@@ -13,8 +13,8 @@ upstream one (graphdeco-inria/diff-gaussian-rasterization, diff_gaussian_rasteri
 plus `rasterize_views(...)`: many cameras over one Gaussian set in one launch sequence (the
 throughput path: per-Gaussian inputs are read once per batch).
 
-Differentiable like upstream: when grad mode is on and an input requires grad, the call goes through an autograd
-Function (_RasterizeViews) whose backward is the HIP backward of include/gaussreg_hip.h (gr_raster_backward): gradients
+Differentiable like upstream: when grad mode is on and an input requires grad, the call goes through the autograd
+Function (_Rasterize) whose backward is the HIP backward of include/gaussreg_hip.h (gr_raster_backward): gradients
 for means3D, means2D (dL/dNDC), shs / colors_precomp, opacities, scales / rotations / cov3D_precomp; radii is not
 differentiable.  Otherwise every call takes the forward-only path, unchanged.
 
@@ -65,7 +65,6 @@ def _flags(fast_exp):
     global _ENV_FAST
     if fast_exp is None:
         if _ENV_FAST is None:
-            import os
             _ENV_FAST = os.environ.get("GR_RASTER_FAST_EXP", "0")[:1] == "1"
         fast_exp = _ENV_FAST
     return FAST_EXP if fast_exp else 0
@@ -120,11 +119,15 @@ class ViewBatch:
         return out
 
 
-def _dev_f32(t: Optional[torch.Tensor], dev, name):
+def _dev_f32(t: Optional[torch.Tensor], dev, name, grad=False):
+    """fp32, contiguous, on `dev`.  `grad`: a differentiable conversion (no detach), so gradients reach the caller's tensor
+    in its own dtype and device."""
     if t is None:
         return None
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a tensor")
+    if grad:
+        return t.to(device=dev, dtype=torch.float32).contiguous()
     if t.device == dev and t.dtype == torch.float32 and t.is_contiguous():
         return t  # only its pointer is read
     return t.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -216,6 +219,17 @@ def _frame_pipe(dev, static_scene):
 _geom_bytes = {}
 
 
+def _geom_size(L, P, V, W, H):
+    """Bytes of the geometry buffer of a call of this shape (gr_raster_geom_bytes + slack), asked once per shape."""
+    gkey = (P, V, W, H)
+    gbytes = _geom_bytes.get(gkey)
+    if gbytes is None:
+        if len(_geom_bytes) > 64:
+            _geom_bytes.clear()
+        gbytes = _geom_bytes[gkey] = L.gr_raster_geom_bytes(P, V, W, H) + 256
+    return gbytes
+
+
 def reset_frame_pipe():
     """Drop this thread's frame pipes: the references they keep to the last frame's input tensors (see _FramePipe) and the
     readiness events.  The next one-camera call starts with a full wait on the caller's stream."""
@@ -225,301 +239,142 @@ def reset_frame_pipe():
             p.stamp = p.keep = p.ready = p.ptrs = None
 
 
-def _dev_f32_grad(t, dev):
-    """_dev_f32 for the autograd path: a differentiable conversion (no detach), so gradients reach the caller's tensor in
-    its own dtype and device."""
-    if t is None:
-        return None
-    if not isinstance(t, torch.Tensor):
-        raise TypeError("rasterizer inputs must be tensors")
-    return t.to(device=dev, dtype=torch.float32).contiguous()
+# The per-Gaussian inputs in the order of the C ABI (include/gaussreg_hip.h): every tuple of them below is in this order.
+_SCENE = ("means3D", "shs", "colors_precomp", "opacities", "scales", "rotations", "cov3D_precomp")
+_GRADS = ("means3D", "means2D") + _SCENE[1:]  # the eight gradient outputs, in the order of the C ABI
+_CAMERA = ("viewmatrix", "projmatrix", "campos")
+_CAMERA_SHAPES = ((4, 4), (4, 4), (3,))
+# _Rasterize.forward's arguments after ctx: backward finds needs_input_grad, and places its gradients, by these names
+_ARGS = ("vb", "flags", "aux", "one", "box", "means2D") + _SCENE + _CAMERA
+# (aux, a camera tensor needs grad) -> the backward entry point; its scratch size comes from <name>_bytes
+_BACKWARD = {(False, False): "gr_raster_backward", (True, False): "gr_raster_backward_aux",
+             (False, True): "gr_raster_backward_cam", (True, True): "gr_raster_backward_cam"}
 
 
-class _RasterizeViews(torch.autograd.Function):
-    """Autograd forward (gr_raster_preprocess + gr_raster_render_keep, serial, on the caller's stream) and HIP backward
-    (gr_raster_backward).  Inputs arrive as fp32, contiguous, on the device (converted differentiably by the caller).
-    vmat / pmat / cpos: ViewBatch.camera_inputs, present only when a camera tensor requires grad; the backward then is
-    gr_raster_backward_cam."""
-
-    @staticmethod
-    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov, vmat=None, pmat=None, cpos=None):
-        dev = m.device
-        L = _lib.lib()
-        V, views, H, W = vb.count, vb.array, vb.height, vb.width
-        P = m.shape[0]
-        M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
-        st = _lib.stream_ptr(dev)
-        nr = (ctypes.c_int64 * (V + 1))()
-        hw = H * W
-        state = torch.empty(5 * V * hw, dtype=torch.float32, device=dev)  # colour, final_T, n_contrib (gr_raster_render_keep)
-        radii = torch.empty((V, P), dtype=torch.int32, device=dev)
-        gbytes = L.gr_raster_geom_bytes(P, V, W, H) + 256
-        geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-        ptrs = (_lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov))
-        _lib.check(L.gr_raster_preprocess(P, M, *ptrs, views, V, _lib.ptr(radii), _lib.ptr(geom), gbytes, nr, st))
-        total = sum(int(nr[v]) for v in range(V))
-        binb = torch.empty(L.gr_raster_bin_bytes(total, W, H, V) + 256, dtype=torch.uint8, device=dev)
-        _lib.check(L.gr_raster_render_keep(P, views, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel(),
-                                           _lib.ptr(state), flags, st))
-        ctx.vb, ctx.flags, ctx.one, ctx.M, ctx.nr = vb, flags, one, M, nr
-        ctx.geom, ctx.binb, ctx.state = geom, binb, state[3 * V * hw:]  # final_T, n_contrib
-        ctx.m2d = None if m2d is None else (m2d.shape, m2d.dtype, m2d.device)
-        ctx.save_for_backward(m, op, sh, cp, sc, rot, cov)
-        # a tensor of its own (not a view of the state allocation): callers may modify the image in place, as upstream's
-        color = state[:3 * V * hw].view((3, H, W) if one else (V, 3, H, W)).clone()
-        radii = radii.view(P) if one else radii
-        ctx.mark_non_differentiable(radii)
-        box.extend(int(nr[v]) for v in range(V))  # num_rendered (not an autograd output)
-        return color, radii
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_color, grad_radii):
-        m, op, sh, cp, sc, rot, cov = ctx.saved_tensors
-        dev = m.device
-        L = _lib.lib()
-        vb = ctx.vb
-        V, H, W = vb.count, vb.height, vb.width
-        P = m.shape[0]
-        need = ctx.needs_input_grad
-        if grad_color is None:
-            grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
-        g = grad_color.to(device=dev, dtype=torch.float32).contiguous()
-
-        def out(t, i):
-            return torch.empty_like(t) if (t is not None and need[i]) else None
-        dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
-                                             out(cov, 11))
-        dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
-        dcam = _camera_outputs(need, V, dev)
-        hw = H * W
-        final_T = ctx.state[:V * hw]
-        n_contrib = ctx.state[V * hw:]
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            if dcam is not None:
-                sbytes = L.gr_raster_backward_cam_bytes(P, V, W, H, ctx.nr, BWD_COLOR_ONLY) + 256
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.gr_raster_backward_cam(
-                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
-                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
-                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), None, None, ctx.flags | BWD_COLOR_ONLY,
-                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
-                    _lib.ptr(dcov), _lib.ptr(dcam[0]), _lib.ptr(dcam[1]), _lib.ptr(dcam[2]), _lib.ptr(scratch),
-                    scratch.numel(), st))
-            else:
-                sbytes = L.gr_raster_backward_bytes(P, V, W, H, ctx.nr) + 256
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.gr_raster_backward(
-                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
-                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
-                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(g), ctx.flags, _lib.ptr(dm), _lib.ptr(dm2),
-                    _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot), _lib.ptr(dcov),
-                    _lib.ptr(scratch), scratch.numel(), st))
-        if dm2 is not None:
-            shape, dtype, device = ctx.m2d
-            dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
-        return (None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov) + (dcam or (None, None, None))
+def _sh_coeffs(sh, P):
+    """M of the C ABI: SH coefficients per Gaussian of a (P, M, 3) or flat `shs` (0 with colors_precomp)."""
+    return 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
 
 
-def _camera_outputs(need, V, dev):
-    """Gradient buffers for the camera inputs (positions 12 .. 14 of the autograd Functions) that need one; None when
-    none does: the backward then is the call without camera gradients."""
-    if len(need) < 15 or not any(need[12:15]):
-        return None
-    return tuple(torch.empty((V,) + shape, dtype=torch.float32, device=dev) if need[12 + k] else None
-                 for k, shape in enumerate(((4, 4), (4, 4), (3,))))
-
-
-def _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, keep):
-    """gr_raster_preprocess + gr_raster_render_aux, serial, on the caller's stream.  Inputs: fp32, contiguous, on the device.
-    Returns (color, radii, depth, alpha, num_rendered array, M, geom, bin, state); state (final_T, n_contrib) only with
-    `keep`.  Every map is a tensor of its own."""
+def _render_serial(vb, flags, one, inputs, aux, keep):
+    """gr_raster_preprocess + render, serial, on the caller's stream.  `inputs`: _SCENE, fp32, contiguous, on the device.
+    `aux`: also the depth and alpha maps (gr_raster_render_aux; otherwise gr_raster_render_keep, which always keeps).
+    `keep`: the render also writes final_T and n_contrib for a backward.
+    Returns (color, radii[, depth, alpha]), the num_rendered array and (M, geom, bin, state) for the backward; state =
+    final_T, n_contrib of all views (None without `keep`).  Every output is a tensor of its own."""
+    m = inputs[0]
     dev = m.device
     L = _lib.lib()
     V, views, H, W = vb.count, vb.array, vb.height, vb.width
     P = m.shape[0]
-    M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
+    M = _sh_coeffs(inputs[1], P)
     st = _lib.stream_ptr(dev)
     nr = (ctypes.c_int64 * (V + 1))()
-    color = torch.empty((3, H, W) if one else (V, 3, H, W), dtype=torch.float32, device=dev)
-    depth = torch.empty((1, H, W) if one else (V, 1, H, W), dtype=torch.float32, device=dev)
-    alpha = torch.empty_like(depth)
-    state = torch.empty(2 * V * H * W, dtype=torch.float32, device=dev) if keep else None
+    hw = H * W
+    if aux:
+        color = torch.empty((3, H, W) if one else (V, 3, H, W), dtype=torch.float32, device=dev)
+        depth = torch.empty((1, H, W) if one else (V, 1, H, W), dtype=torch.float32, device=dev)
+        alpha = torch.empty_like(depth)
+        state = torch.empty(2 * V * hw, dtype=torch.float32, device=dev) if keep else None
+    else:
+        # colour, final_T, n_contrib (gr_raster_render_keep)
+        block = torch.empty(5 * V * hw, dtype=torch.float32, device=dev)
     radii = torch.empty((P,) if one else (V, P), dtype=torch.int32, device=dev)
-    gbytes = L.gr_raster_geom_bytes(P, V, W, H) + 256
+    gbytes = _geom_size(L, P, V, W, H)
     geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-    ptrs = (_lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot), _lib.ptr(cov))
-    _lib.check(L.gr_raster_preprocess(P, M, *ptrs, views, V, _lib.ptr(radii), _lib.ptr(geom), gbytes, nr, st))
-    total = sum(int(nr[v]) for v in range(V))
-    binb = torch.empty(L.gr_raster_bin_bytes(total, W, H, V) + 256, dtype=torch.uint8, device=dev)
-    _lib.check(L.gr_raster_render_aux(P, views, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel(),
-                                      _lib.ptr(color), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(state), flags, st))
-    return color, radii, depth, alpha, nr, M, geom, binb, state
+    _lib.check(L.gr_raster_preprocess(P, M, *map(_lib.ptr, inputs), views, V, _lib.ptr(radii), _lib.ptr(geom), gbytes, nr,
+                                      st))
+    binb = torch.empty(L.gr_raster_bin_bytes(sum(nr[:V]), W, H, V) + 256, dtype=torch.uint8, device=dev)
+    shared = (P, views, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel())
+    if aux:
+        _lib.check(L.gr_raster_render_aux(*shared, _lib.ptr(color), _lib.ptr(depth), _lib.ptr(alpha), _lib.ptr(state), flags,
+                                          st))
+        return (color, radii, depth, alpha), nr, (M, geom, binb, state)
+    _lib.check(L.gr_raster_render_keep(*shared, _lib.ptr(block), flags, st))
+    # a tensor of its own (not a view of the state allocation): callers may modify the image in place, as upstream's
+    color = block[:3 * V * hw].view((3, H, W) if one else (V, 3, H, W)).clone()
+    return (color, radii), nr, (M, geom, binb, block[3 * V * hw:])
 
 
-class _RasterizeViewsAux(torch.autograd.Function):
-    """_RasterizeViews with the depth and alpha maps: forward gr_raster_preprocess + gr_raster_render_aux, backward
-    gr_raster_backward_aux.  Output gradients autograd did not produce are passed as null pointers."""
+class _Rasterize(torch.autograd.Function):
+    """Autograd forward (_render_serial with `keep`) and HIP backward: gr_raster_backward, gr_raster_backward_aux with the
+    depth and alpha maps (`aux`), gr_raster_backward_cam when a camera tensor requires grad.  The Gaussian inputs arrive
+    as fp32, contiguous, on the device (converted differentiably by the caller); viewmatrix / projmatrix / campos:
+    ViewBatch.camera_inputs, or None.  `box` receives num_rendered (not an autograd output)."""
 
     @staticmethod
-    def forward(ctx, vb, flags, one, box, m, m2d, op, sh, cp, sc, rot, cov, vmat=None, pmat=None, cpos=None):
-        color, radii, depth, alpha, nr, M, geom, binb, state = _render_aux(vb, flags, one, m, op, sh, cp, sc, rot, cov, True)
-        ctx.vb, ctx.flags, ctx.M, ctx.nr = vb, flags, M, nr
-        ctx.geom, ctx.binb, ctx.state = geom, binb, state
-        ctx.m2d = None if m2d is None else (m2d.shape, m2d.dtype, m2d.device)
-        ctx.save_for_backward(m, op, sh, cp, sc, rot, cov)
-        ctx.mark_non_differentiable(radii)
-        box.extend(int(nr[v]) for v in range(vb.count))
-        return color, radii, depth, alpha
+    def forward(ctx, vb, flags, aux, one, box, means2D, *scene_and_cameras):
+        inputs = scene_and_cameras[:len(_SCENE)]
+        outs, nr, (ctx.M, ctx.geom, ctx.binb, ctx.state) = _render_serial(vb, flags, one, inputs, aux, True)
+        ctx.vb, ctx.flags, ctx.aux, ctx.nr = vb, flags, aux, nr
+        ctx.m2d = None if means2D is None else (means2D.shape, means2D.dtype, means2D.device)
+        ctx.save_for_backward(*inputs)
+        ctx.mark_non_differentiable(outs[1])
+        box.extend(nr[:vb.count])
+        return outs
 
     @staticmethod
     @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_color, grad_radii, grad_depth, grad_alpha):
-        m, op, sh, cp, sc, rot, cov = ctx.saved_tensors
-        dev = m.device
+    def backward(ctx, grad_color, grad_radii, grad_depth=None, grad_alpha=None):
+        inputs = ctx.saved_tensors
+        dev = inputs[0].device
         L = _lib.lib()
-        vb = ctx.vb
+        vb, aux = ctx.vb, ctx.aux
         V, H, W = vb.count, vb.height, vb.width
-        P = m.shape[0]
-        need = ctx.needs_input_grad
-
-        def grad(t):
-            return None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-        gc, gd, ga = grad(grad_color), grad(grad_depth), grad(grad_alpha)
-
-        def out(t, i):
-            return torch.empty_like(t) if (t is not None and need[i]) else None
-        dm, dop, dsh, dcp, dsc, drot, dcov = (out(m, 4), out(op, 6), out(sh, 7), out(cp, 8), out(sc, 9), out(rot, 10),
-                                             out(cov, 11))
-        dm2 = torch.empty((V, P, 3), dtype=torch.float32, device=dev) if need[5] else None
-        dcam = _camera_outputs(need, V, dev)
+        P = inputs[0].shape[0]
+        need = dict(zip(_ARGS, ctx.needs_input_grad))
+        # output gradients autograd did not produce: zeros for the colour-only backward, null pointers for the maps
+        if grad_color is None and not aux:
+            grad_color = torch.zeros((V, 3, H, W), dtype=torch.float32, device=dev)
+        gc, gd, ga = (None if g is None else g.to(device=dev, dtype=torch.float32).contiguous()
+                      for g in (grad_color, grad_depth, grad_alpha))
+        grads = dict.fromkeys(_ARGS)
+        for name, t in zip(_SCENE, inputs):
+            if t is not None and need[name]:
+                grads[name] = torch.empty_like(t)
+        if need["means2D"]:
+            grads["means2D"] = torch.empty((V, P, 3), dtype=torch.float32, device=dev)
+        cam = False
+        for name, shape in zip(_CAMERA, _CAMERA_SHAPES):
+            if need[name]:
+                cam = True
+                grads[name] = torch.empty((V,) + shape, dtype=torch.float32, device=dev)
         hw = H * W
-        final_T = ctx.state[:V * hw]
-        n_contrib = ctx.state[V * hw:]
+        final_T, n_contrib = ctx.state[:V * hw], ctx.state[V * hw:]
+        # the three entry points share their argument list up to dL_dcolor and from the flags on; the map gradients
+        # (aux, cam) and the camera outputs (cam) are spliced in.  Without the maps, cam gets null map gradients and
+        # GR_RASTER_BWD_COLOR_ONLY, in its scratch layout too.
+        entry = _BACKWARD[aux, cam]
+        color_only = BWD_COLOR_ONLY if cam and not aux else 0
+        maps = (_lib.ptr(gd), _lib.ptr(ga)) if aux or cam else ()
+        outs = [_lib.ptr(grads[name]) for name in (_GRADS + _CAMERA if cam else _GRADS)]
         with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            if dcam is not None:
-                sbytes = L.gr_raster_backward_cam_bytes(P, V, W, H, ctx.nr, 0) + 256
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.gr_raster_backward_cam(
-                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
-                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
-                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags,
-                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
-                    _lib.ptr(dcov), _lib.ptr(dcam[0]), _lib.ptr(dcam[1]), _lib.ptr(dcam[2]), _lib.ptr(scratch),
-                    scratch.numel(), st))
-            else:
-                sbytes = L.gr_raster_backward_aux_bytes(P, V, W, H, ctx.nr) + 256
-                scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
-                _lib.check(L.gr_raster_backward_aux(
-                    P, ctx.M, _lib.ptr(m), _lib.ptr(sh), _lib.ptr(cp), _lib.ptr(op), _lib.ptr(sc), _lib.ptr(rot),
-                    _lib.ptr(cov), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb), ctx.binb.numel(),
-                    ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), _lib.ptr(gd), _lib.ptr(ga), ctx.flags,
-                    _lib.ptr(dm), _lib.ptr(dm2), _lib.ptr(dsh), _lib.ptr(dcp), _lib.ptr(dop), _lib.ptr(dsc), _lib.ptr(drot),
-                    _lib.ptr(dcov), _lib.ptr(scratch), scratch.numel(), st))
-        if dm2 is not None:
+            sbytes = getattr(L, entry + "_bytes")(P, V, W, H, ctx.nr, *((color_only,) if cam else ())) + 256
+            scratch = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+            _lib.check(getattr(L, entry)(
+                P, ctx.M, *map(_lib.ptr, inputs), vb.array, V, _lib.ptr(ctx.geom), ctx.geom.numel(), _lib.ptr(ctx.binb),
+                ctx.binb.numel(), ctx.nr, _lib.ptr(final_T), _lib.ptr(n_contrib), _lib.ptr(gc), *maps,
+                ctx.flags | color_only, *outs,
+                _lib.ptr(scratch), scratch.numel(), _lib.stream_ptr(dev)))
+        if grads["means2D"] is not None:
             shape, dtype, device = ctx.m2d
-            dm2 = dm2.reshape(shape).to(device=device, dtype=dtype)
-        return (None, None, None, None, dm, dm2, dop, dsh, dcp, dsc, drot, dcov) + (dcam or (None, None, None))
+            grads["means2D"] = grads["means2D"].reshape(shape).to(device=device, dtype=dtype)
+        return tuple([grads[name] for name in _ARGS])
 
 
 def _wants_grad(*ts):
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
 
-def rasterize_views(settings, means3D, opacities, shs=None,
-                    colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, fast_exp=None, _one=False,
-                    static_scene=False, *, means2D=None, render_depth=False):
-    """Render the same Gaussians from len(settings) cameras (`settings`: a sequence of
-    GaussianRasterizationSettings, or a prebuilt ViewBatch).
-
-    Returns (color (V,3,H,W) f32, radii (V,P) i32, num_rendered list[int]).  num_rendered = (tile, Gaussian)
-    instances actually binned per view: at most the reference's count (pairs that cannot reach alpha = 1/255
-    anywhere in the tile are dropped before the sort; the image is unaffected).
-
-    `fast_exp=True`: the blend uses the hardware exponential (v_exp_f32) instead of the deterministic polynomial of the
-    oracle -- the image is within 1e-5 relative of the bit-exact one (default False: bit-exact).
-    `static_scene=True` (extension): consecutive calls over the same, unmodified scene tensors overlap on two internal
-    streams (_FramePipe: read its contract first -- only writes that bump the tensors' version counters are seen).
-    (`_one`: internal, one camera -- the outputs come back as (3,H,W) and (P,), no view ops on the way out.)
-
-    Autograd: when grad mode is on and any input requires grad, the call is differentiable (see the module docstring);
-    the `viewmatrix`, `projmatrix` and `campos` tensors of the settings (or of the settings a ViewBatch was built from)
-    count as inputs.  It then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
-    `means2D` (keyword only, extension): a (V, P, 3) tensor (upstream's (P, 3) screen-space means for one camera) whose
-    .grad receives dL/d(NDC position) per view; its values are not read.
-
-    `render_depth=True` (keyword only): returns (color, radii, num_rendered, depth, alpha) with depth and alpha of shape
-    (V,1,H,W) fp32: depth = sum_i w_i z_i over the entries the colour blend blends (w_i its weights, z_i the view-space
-    depth; the background adds nothing), alpha = 1 - final transmittance.  color and radii are bit-identical to the
-    call without it.  Differentiable like the colour.  The call runs serially on the caller's stream with and without
-    grad: `static_scene` is ignored on this path."""
-    dev = means3D.device if means3D.is_cuda else _lib.require_gpu()
+def _render_pipelined(vb, flags, one, inputs, static_scene):
+    """The forward-only colour path: one gr_raster_forward per frame, on the frame pipe's side streams when the caller
+    opted in (_FramePipe).  `inputs`: _SCENE, fp32, contiguous, on the device.  Returns (color, radii, num_rendered)."""
+    m, sh, cp, op, sc, rot, cov = inputs
+    dev = m.device
     L = _lib.lib()
-    n_pts = int(means3D.shape[0])
-
-    def given(t):  # upstream passes empty tensors for "not provided"; with zero Gaussians everything is empty
-        return t is not None and (t.numel() > 0 or n_pts == 0)
-
-    if given(shs) == given(colors_precomp):
-        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
-    has_sr = given(scales) and given(rotations)
-    has_cov = given(cov3D_precomp)
-    if has_sr == has_cov or (given(scales) != given(rotations)):
-        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
-    vb = settings if isinstance(settings, ViewBatch) else ViewBatch(settings)
-    cam_grad = vb.wants_grad()
-    if cam_grad or _wants_grad(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp):
-        if means3D.dim() != 2 or means3D.shape[1] != 3:
-            raise RuntimeError("means3D must have dimensions (num_points, 3)")
-        if means2D is not None:
-            ok = (tuple(means2D.shape) == (vb.count, n_pts, 3) or
-                  (vb.count == 1 and tuple(means2D.shape) == (n_pts, 3)))
-            if not ok:
-                raise ValueError(f"means2D must have shape ({vb.count}, {n_pts}, 3)" +
-                                 (f" or ({n_pts}, 3)" if vb.count == 1 else "") + f", got {tuple(means2D.shape)}")
-        home = torch.cuda.current_device()
-        if home != dev.index:
-            torch.cuda.set_device(dev)
-        box = []
-        try:
-            res = (_RasterizeViewsAux if render_depth else _RasterizeViews).apply(
-                vb, _flags(fast_exp), _one and vb.count == 1, box, _dev_f32_grad(means3D, dev), means2D,
-                _dev_f32_grad(opacities, dev), _dev_f32_grad(shs, dev) if given(shs) else None,
-                _dev_f32_grad(colors_precomp, dev) if given(colors_precomp) else None,
-                _dev_f32_grad(scales, dev) if has_sr else None, _dev_f32_grad(rotations, dev) if has_sr else None,
-                _dev_f32_grad(cov3D_precomp, dev) if has_cov else None,
-                *(vb.camera_inputs(dev) if cam_grad else ()))
-        finally:
-            if home != dev.index:
-                torch.cuda.set_device(home)
-        if render_depth:
-            return res[0], res[1], box, res[2], res[3]
-        return res[0], res[1], box
     V, views, H, W = vb.count, vb.array, vb.height, vb.width
-    m = _dev_f32(means3D, dev, "means3D")
-    if m.dim() != 2 or m.shape[1] != 3:
-        raise RuntimeError("means3D must have dimensions (num_points, 3)")
     P = m.shape[0]
-    op = _dev_f32(opacities, dev, "opacities")
-    sh = _dev_f32(shs, dev, "shs") if given(shs) else None
-    cp = _dev_f32(colors_precomp, dev, "colors_precomp") if given(colors_precomp) else None
-    sc = _dev_f32(scales, dev, "scales") if has_sr else None
-    rot = _dev_f32(rotations, dev, "rotations") if has_sr else None
-    cov = _dev_f32(cov3D_precomp, dev, "cov3D_precomp") if has_cov else None
-    if render_depth:
-        home = torch.cuda.current_device()
-        if home != dev.index:
-            torch.cuda.set_device(dev)
-        try:
-            color, radii, depth, alpha, nr = _render_aux(vb, _flags(fast_exp), _one and V == 1, m, op, sh, cp, sc, rot, cov,
-                                                         False)[:5]
-        finally:
-            if home != dev.index:
-                torch.cuda.set_device(home)
-        return color, radii, [int(nr[v]) for v in range(V)], depth, alpha
-    M = 0 if sh is None else (sh.shape[1] if sh.dim() == 3 else sh.reshape(max(P, 1), -1, 3).shape[1])
+    M = _sh_coeffs(sh, P)
     nr = (ctypes.c_int64 * (V + 1))()
     pipe = _frame_pipe(dev, static_scene)
     cur = side = None
@@ -535,17 +390,10 @@ def rasterize_views(settings, means3D, opacities, shs=None,
             st = ctypes.c_void_p(side.cuda_stream)
         else:
             st = _lib.stream_ptr(dev)
-        one = _one and V == 1
         color = torch.empty((3, H, W) if one else (V, 3, H, W), dtype=torch.float32, device=dev)
         radii = torch.empty((P,) if one else (V, P), dtype=torch.int32, device=dev)  # every entry is written by preprocess
-        gkey = (P, V, W, H)
-        gbytes = _geom_bytes.get(gkey)
-        if gbytes is None:
-            if len(_geom_bytes) > 64:
-                _geom_bytes.clear()
-            gbytes = _geom_bytes[gkey] = L.gr_raster_geom_bytes(P, V, W, H) + 256
+        gbytes = _geom_size(L, P, V, W, H)
         geom = torch.empty(gbytes, dtype=torch.uint8, device=dev)
-        flags = _flags(fast_exp)
         # the binning buffer is sized from the last call of this shape (+ 25 %): the library is entered once per frame, and
         # only a frame that needs more comes back for a larger buffer
         key = (dev.index, P, V, W, H)
@@ -581,8 +429,7 @@ def rasterize_views(settings, means3D, opacities, shs=None,
             if rc == _lib.GR_RETRY_FULL:
                 rc = forward(flags)
         _lib.check(rc, allow=(_lib.GR_RETRY_BIN,))
-        total = sum(int(nr[v]) for v in range(V))
-        need = L.gr_raster_bin_bytes(total, W, H, V)
+        need = L.gr_raster_bin_bytes(sum(nr[:V]), W, H, V)
         if rc == _lib.GR_RETRY_BIN:
             binb = torch.empty(need + 256, dtype=torch.uint8, device=dev)
             _lib.check(L.gr_raster_render_ex(P, views, V, nr, _lib.ptr(geom), geom.numel(), _lib.ptr(binb), binb.numel(),
@@ -604,7 +451,86 @@ def rasterize_views(settings, means3D, opacities, shs=None,
     finally:
         if home != dev.index:
             torch.cuda.set_device(home)
-    return color, radii, [int(nr[v]) for v in range(V)]
+    return color, radii, nr[:V]
+
+
+def rasterize_views(settings, means3D, opacities, shs=None,
+                    colors_precomp=None, scales=None, rotations=None, cov3D_precomp=None, fast_exp=None, _one=False,
+                    static_scene=False, *, means2D=None, render_depth=False):
+    """Render the same Gaussians from len(settings) cameras (`settings`: a sequence of
+    GaussianRasterizationSettings, or a prebuilt ViewBatch).
+
+    Returns (color (V,3,H,W) f32, radii (V,P) i32, num_rendered list[int]).  num_rendered = (tile, Gaussian)
+    instances actually binned per view: at most the reference's count (pairs that cannot reach alpha = 1/255
+    anywhere in the tile are dropped before the sort; the image is unaffected).
+
+    `fast_exp=True`: the blend uses the hardware exponential (v_exp_f32) instead of the deterministic polynomial of the
+    oracle -- the image is within 1e-5 relative of the bit-exact one (default False: bit-exact).
+    `static_scene=True` (extension): consecutive calls over the same, unmodified scene tensors overlap on two internal
+    streams (_FramePipe: read its contract first -- only writes that bump the tensors' version counters are seen).
+    (`_one`: internal, one camera -- the outputs come back as (3,H,W) and (P,), no view ops on the way out.)
+
+    Autograd: when grad mode is on and any input requires grad, the call is differentiable (see the module docstring);
+    the `viewmatrix`, `projmatrix` and `campos` tensors of the settings (or of the settings a ViewBatch was built from)
+    count as inputs.  It then runs serially on the caller's stream (`static_scene` is ignored) and keeps its buffers for the backward.
+    `means2D` (keyword only, extension): a (V, P, 3) tensor (upstream's (P, 3) screen-space means for one camera) whose
+    .grad receives dL/d(NDC position) per view; its values are not read.
+
+    `render_depth=True` (keyword only): returns (color, radii, num_rendered, depth, alpha) with depth and alpha of shape
+    (V,1,H,W) fp32: depth = sum_i w_i z_i over the entries the colour blend blends (w_i its weights, z_i the view-space
+    depth; the background adds nothing), alpha = 1 - final transmittance.  color and radii are bit-identical to the
+    call without it.  Differentiable like the colour.  The call runs serially on the caller's stream with and without
+    grad: `static_scene` is ignored on this path."""
+    dev = means3D.device if means3D.is_cuda else _lib.require_gpu()
+    n_pts = int(means3D.shape[0])
+
+    def given(t):  # upstream passes empty tensors for "not provided"; with zero Gaussians everything is empty
+        return t is not None and (t.numel() > 0 or n_pts == 0)
+
+    has_sh, has_cp = given(shs), given(colors_precomp)
+    has_sc, has_rot, has_cov = given(scales), given(rotations), given(cov3D_precomp)
+    if has_sh == has_cp:
+        raise Exception('Please provide excatly one of either SHs or precomputed colors!')
+    has_sr = has_sc and has_rot
+    if has_sr == has_cov or has_sc != has_rot:
+        raise Exception('Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!')
+    vb = settings if isinstance(settings, ViewBatch) else ViewBatch(settings)
+    cam_grad = vb.wants_grad()
+    grad = cam_grad or _wants_grad(means3D, means2D, opacities, shs, colors_precomp, scales, rotations, cov3D_precomp)
+    if means3D.dim() != 2 or means3D.shape[1] != 3:
+        raise RuntimeError("means3D must have dimensions (num_points, 3)")
+    if grad and means2D is not None:
+        ok = (tuple(means2D.shape) == (vb.count, n_pts, 3) or
+              (vb.count == 1 and tuple(means2D.shape) == (n_pts, 3)))
+        if not ok:
+            raise ValueError(f"means2D must have shape ({vb.count}, {n_pts}, 3)" +
+                             (f" or ({n_pts}, 3)" if vb.count == 1 else "") + f", got {tuple(means2D.shape)}")
+    # under grad the conversion is part of the graph; otherwise only the pointers are read
+    inputs = (_dev_f32(means3D, dev, "means3D", grad),
+              _dev_f32(shs, dev, "shs", grad) if has_sh else None,
+              _dev_f32(colors_precomp, dev, "colors_precomp", grad) if has_cp else None,
+              _dev_f32(opacities, dev, "opacities", grad),
+              _dev_f32(scales, dev, "scales", grad) if has_sr else None,
+              _dev_f32(rotations, dev, "rotations", grad) if has_sr else None,
+              _dev_f32(cov3D_precomp, dev, "cov3D_precomp", grad) if has_cov else None)  # (_SCENE)
+    flags, one = _flags(fast_exp), _one and vb.count == 1
+    if not (grad or render_depth):
+        return _render_pipelined(vb, flags, one, inputs, static_scene)
+    home = torch.cuda.current_device()
+    if home != dev.index:
+        torch.cuda.set_device(dev)
+    try:
+        if grad:
+            num_rendered = []
+            outs = _Rasterize.apply(vb, flags, render_depth, one, num_rendered, means2D, *inputs,
+                                    *(vb.camera_inputs(dev) if cam_grad else (None, None, None)))
+        else:
+            outs, nr, _ = _render_serial(vb, flags, one, inputs, True, False)
+            num_rendered = nr[:vb.count]
+    finally:
+        if home != dev.index:
+            torch.cuda.set_device(home)
+    return (outs[0], outs[1], num_rendered) + tuple(outs[2:])
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
