@@ -95,6 +95,12 @@ SIGNATURES.update({
     "gr_kpconv_plan": (c_int, [c_i64] * 6 + [c_int]),
     "gr_kpconv_forward": (c_int, [c_void] * 4 + [c_i64] * 5 + [c_void, c_i64, c_void, c_void, c_f32, c_f32, c_void,
                                                             c_void, c_size, c_void]),
+    "gr_kpconv_backward_plan": (c_int, [c_i64] * 6 + [c_int, c_i64]),
+    "gr_kpconv_backward_workspace_bytes": (c_size, [c_i64] * 6 + [c_int, c_i64]),
+    "gr_kpconv_backward": (c_int, [c_void] * 4 + [c_i64] * 5 + [c_void, c_i64, c_void, c_f32, c_f32] + [c_void] * 6 +
+                           [c_i64, c_void, c_size, c_void]),
+    "gr_neighbor_pool_backward": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_int] + [c_void] * 4 +
+                                  [c_void, c_size, c_void]),
     "gr_gather_rows": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_void, c_void, c_void]),
     "gr_neighbor_pool": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_int, c_void, c_void]),
     "gr_group_norm_workspace_bytes": (c_size, [c_i64]),

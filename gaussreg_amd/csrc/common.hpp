@@ -215,6 +215,14 @@ int depth_sort_views(const uint32_t* field, const uint32_t* rect_raw, uint64_t* 
 // valid -- repeat with key_mm = null.
 bool depth_sort_msd_possible(int64_t P, int V, int key_bits);
 
+// kpconv.hip: the forward's row-flag and gather launches (WF (m, K*Cin) and max(neighbor_num, 1) per query), reused by the
+// backward pass.  `plan` is gr_kpconv_plan's value for the same sizes; flag has n bytes.
+void kpconv_rowflag_launch(const float* s_feats, int64_t n, int64_t cin, uint8_t* flag, hipStream_t stream);
+void kpconv_gather_launch(int plan, const float* s_feats, const float* q_points, const float* s_points,
+                          const int64_t* neighbor_indices, int64_t n, int64_t m, int64_t h, int64_t cin, int64_t k,
+                          const float* kernel_points, float sigma, float inf, const uint8_t* flag, float* WF, float* num,
+                          hipStream_t stream);
+
 // Optional per-kernel HIP-event timing (off by default; bench.py turns it on to measure the
 // dominant kernel's average launch duration on the stream it is launched on).
 struct KernelTimer {

@@ -466,6 +466,39 @@ __global__ __launch_bounds__(256) void pool4_kernel(const float4* __restrict__ x
 }  // namespace
 }  // namespace gr
 
+// The two launches that turn (features, points, neighbours) into WF (m, K*Cin) and max(neighbor_num, 1) per query, shared
+// with the backward pass (kpconv_backward.hip recomputes WF with the forward's own kernels).  `plan`: gr_kpconv_plan's value.
+namespace gr {
+void kpconv_rowflag_launch(const float* s_feats, int64_t n, int64_t cin, uint8_t* flag, hipStream_t stream) {
+  hipLaunchKernelGGL(rowflag_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, s_feats, (int)n, (int)cin, flag);
+}
+
+void kpconv_gather_launch(int plan, const float* s_feats, const float* q_points, const float* s_points,
+                          const int64_t* neighbor_indices, int64_t n, int64_t m, int64_t h, int64_t cin, int64_t k,
+                          const float* kernel_points, float sigma, float inf, const uint8_t* flag, float* WF, float* num,
+                          hipStream_t stream) {
+  const size_t kp_lds = (size_t)std::min<int64_t>(h, KP_HMAX) * (KP_MAX + 2) * sizeof(float);
+#define GR_KP_MFMA(NT)                                                                                                       \
+  hipLaunchKernelGGL((kp_gather_mfma_kernel<NT>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, s_feats, q_points,    \
+                     s_points, neighbor_indices, (int)n, (int)m, (int)h, (int)k, kernel_points, sigma, inf, flag, WF, num)
+#define GR_KP_GENERIC(T)                                                                                                   \
+  hipLaunchKernelGGL((kp_gather_kernel<T>), dim3((unsigned)m), dim3(T), kp_lds, stream, s_feats, q_points, s_points,       \
+                     neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num)
+  switch (plan & GR_KP_GATHER_KERNEL_MASK) {
+    case GR_KP_GATHER_MFMA_1: GR_KP_MFMA(1); break;
+    case GR_KP_GATHER_MFMA_2: GR_KP_MFMA(2); break;
+    case GR_KP_GATHER_MFMA_4: GR_KP_MFMA(4); break;
+    case GR_KP_GATHER_MFMA_8: GR_KP_MFMA(8); break;
+    case GR_KP_GATHER_MFMA_16: GR_KP_MFMA(16); break;
+    case GR_KP_GATHER_T64: GR_KP_GENERIC(64); break;
+    case GR_KP_GATHER_T128: GR_KP_GENERIC(128); break;
+    default: GR_KP_GENERIC(256); break;
+  }
+#undef GR_KP_GENERIC
+#undef GR_KP_MFMA
+}
+}  // namespace gr
+
 using namespace gr;
 
 extern "C" size_t gr_kpconv_workspace_bytes(int64_t n, int64_t m, int64_t k, int64_t cin) {
@@ -533,27 +566,9 @@ extern "C" int gr_kpconv_forward(const float* s_feats, const float* q_points, co
                                   ((reinterpret_cast<uintptr_t>(WF) | reinterpret_cast<uintptr_t>(weights)) & 15) == 0);
   GR_REQUIRE(plan >= 0, "bad sizes");
   KernelTimer timer("kpconv", stream);
-  if (n > 0)
-    hipLaunchKernelGGL(rowflag_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream, s_feats, (int)n, (int)cin, flag);
-  const size_t kp_lds = (size_t)std::min<int64_t>(h, KP_HMAX) * (KP_MAX + 2) * sizeof(float);
-#define GR_KP_MFMA(NT)                                                                                                       \
-  hipLaunchKernelGGL((kp_gather_mfma_kernel<NT>), dim3((unsigned)((m + 3) / 4)), dim3(256), 0, stream, s_feats, q_points,    \
-                     s_points, neighbor_indices, (int)n, (int)m, (int)h, (int)k, kernel_points, sigma, inf, flag, WF, num)
-#define GR_KP_GENERIC(T)                                                                                                   \
-  hipLaunchKernelGGL((kp_gather_kernel<T>), dim3((unsigned)m), dim3(T), kp_lds, stream, s_feats, q_points, s_points,       \
-                     neighbor_indices, (int)n, (int)h, (int)cin, (int)k, kernel_points, sigma, inf, flag, WF, num)
-  switch (plan & GR_KP_GATHER_KERNEL_MASK) {
-    case GR_KP_GATHER_MFMA_1: GR_KP_MFMA(1); break;
-    case GR_KP_GATHER_MFMA_2: GR_KP_MFMA(2); break;
-    case GR_KP_GATHER_MFMA_4: GR_KP_MFMA(4); break;
-    case GR_KP_GATHER_MFMA_8: GR_KP_MFMA(8); break;
-    case GR_KP_GATHER_MFMA_16: GR_KP_MFMA(16); break;
-    case GR_KP_GATHER_T64: GR_KP_GENERIC(64); break;
-    case GR_KP_GATHER_T128: GR_KP_GENERIC(128); break;
-    default: GR_KP_GENERIC(256); break;
-  }
-#undef GR_KP_GENERIC
-#undef GR_KP_MFMA
+  if (n > 0) kpconv_rowflag_launch(s_feats, n, cin, flag, stream);
+  kpconv_gather_launch(plan, s_feats, q_points, s_points, neighbor_indices, n, m, h, cin, k, kernel_points, sigma, inf, flag, WF,
+                       num, stream);
   const int kd = (int)(k * cin);
   const int product = plan >> 8;
   const bool aligned = (product & GR_KP_PRODUCT_ALIGNED) != 0;

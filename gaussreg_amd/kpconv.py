@@ -1,4 +1,5 @@
-"""Mirror of geotransformer/modules/kpconv (forward, inference): KPConv + maxpool + nearest_upsample on HIP.
+"""Mirror of geotransformer/modules/kpconv: KPConv + maxpool + nearest_upsample on HIP -- inference by default, with
+autograd (HIP backward, csrc/kpconv_backward.hip) inside `differentiable()`.
 
 `KPConv` keeps the reference's parameters / buffers (`weights` (K,Cin,Cout), optional `bias`, buffer
 `kernel_points` (K,3)) so reference checkpoints load with the same state-dict keys (kpconv.py:54-65).
@@ -8,7 +9,10 @@ reference reads those 15 points from a PLY asset through open3d, here they are a
 the reference's kernel optimiser, which is not reproduced: such a module must get `kernel_points` passed in or loaded
 from a checkpoint and refuses to run until then.
 """
+import contextlib
 import math
+import threading
+import weakref
 
 import numpy as np
 import torch
@@ -40,6 +44,160 @@ def load_kernels(radius, num_kpoints, dimension=3, fixed='center'):
 
 def _f32(t, dev):
     return (t if t.is_cuda else t.to(dev)).to(torch.float32).contiguous()
+
+
+_mode = threading.local()
+
+
+@contextlib.contextmanager
+def differentiable(chunk_rows=0):
+    """Inside this context, with grad mode on, `KPConv.forward`, `maxpool` and `nearest_upsample` run the same forward
+    kernels as outside it and return tensors with a `grad_fn` whenever `s_feats` / `weights` / `bias` (or `x`) require
+    grad; `KPConvFPN.forward` no longer switches grad off.  Points, kernel points and indices get no gradient: a
+    `q_points` / `s_points` that requires grad raises ValueError.  Outside the context every call is inference, as
+    before.  Thread-local.  `chunk_rows` > 0 overrides the number of queries the KPConv backward processes per chunk
+    (tests)."""
+    old = getattr(_mode, "state", None)
+    _mode.state = (True, int(chunk_rows))
+    try:
+        yield
+    finally:
+        _mode.state = old
+
+
+def differentiable_active():
+    """True inside `differentiable()` while grad mode is on."""
+    return getattr(_mode, "state", None) is not None and torch.is_grad_enabled()
+
+
+_inv_cache = {}
+
+
+def inverted_index(neighbor_indices, n, first_column_only=False):
+    """The inverted neighbour index the backward kernels sum through: (edges, offsets), both int64 on the indices' device.
+    `edges` lists the valid entries of `neighbor_indices` (M, H) as m * H + h, grouped by the support row they name and
+    ascending inside a group (a stable sort of the flattened indices); row r owns edges[offsets[r]:offsets[r + 1]].
+    One neighbour tensor serves several layers, so the result is cached per (tensor, version) for as long as that tensor
+    lives: the entry goes when the tensor does, so no device memory outlives the pyramid it was built for."""
+    stamp = _lib.tensor_stamp([neighbor_indices])
+    key = None if stamp is None else (stamp, tuple(neighbor_indices.shape), int(n), bool(first_column_only))
+    hit = _inv_cache.get(key) if key is not None else None
+    if hit is not None and hit[0]() is not None:  # alive: its address and version are still its own
+        return hit[1], hit[2]
+    with torch.no_grad():
+        M, H = neighbor_indices.shape
+        flat = neighbor_indices.reshape(-1)
+        eid = torch.arange(M * H, device=flat.device, dtype=torch.int64)
+        if first_column_only and H > 0:
+            flat, eid = neighbor_indices[:, 0].contiguous(), eid[::H].contiguous()
+        valid = (flat >= 0) & (flat < n)
+        keys, eid = flat[valid], eid[valid]
+        keys, perm = torch.sort(keys, stable=True)
+        edges = eid[perm].contiguous()
+        offsets = torch.zeros(n + 1, dtype=torch.int64, device=flat.device)
+        if n > 0:
+            offsets[1:] = torch.cumsum(torch.bincount(keys, minlength=n), 0)
+    if key is not None:
+        ref = weakref.ref(neighbor_indices)
+        _inv_cache[key] = (ref, edges, offsets)
+        weakref.finalize(neighbor_indices, _inv_cache_drop, key, ref)
+    return edges, offsets
+
+
+def _inv_cache_drop(key, ref):
+    hit = _inv_cache.get(key)
+    if hit is not None and hit[0] is ref:
+        del _inv_cache[key]
+
+
+def _kpconv_forward(f, q, s, nb, kp, wts, b, sigma, inf):
+    """gr_kpconv_forward on float32 / int64 contiguous tensors of one GPU."""
+    L = _lib.lib()
+    dev = f.device
+    N, Cin = f.shape
+    M, H = nb.shape
+    K, _, Cout = wts.shape
+    out = torch.empty((M, Cout), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = _lib.workspace(dev, L.gr_kpconv_workspace_bytes(N, M, K, Cin))
+        _lib.check(L.gr_kpconv_forward(_lib.ptr(f), _lib.ptr(q), _lib.ptr(s), _lib.ptr(nb), N, M, H, Cin, Cout,
+                                       _lib.ptr(kp), K, _lib.ptr(wts), _lib.ptr(b), float(sigma),
+                                       float(inf), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                       _lib.stream_ptr(dev)))
+    return out
+
+
+class _KPConvFunction(torch.autograd.Function):
+    """Forward: the inference kernels.  Backward: gr_kpconv_backward.  Nothing but the inputs is saved: WF is recomputed."""
+
+    @staticmethod
+    def forward(ctx, f, wts, b, q, s, nb, kp, sigma, inf, chunk_rows):
+        f, wts = f.contiguous(), wts.contiguous()
+        b = None if b is None else b.contiguous()
+        ctx.save_for_backward(f, wts, q, s, nb, kp)
+        ctx.has_bias, ctx.sigma, ctx.inf, ctx.chunk_rows = b is not None, float(sigma), float(inf), int(chunk_rows)
+        return _kpconv_forward(f, q, s, nb, kp, wts, b, sigma, inf)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        f, wts, q, s, nb, kp = ctx.saved_tensors
+        L = _lib.lib()
+        dev = f.device
+        N, Cin = f.shape
+        M, H = nb.shape
+        K, _, Cout = wts.shape
+        go = grad_out.to(torch.float32).contiguous()  # .sum().backward() hands over an expanded zero-stride tensor
+        need_f, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        need_b = ctx.has_bias and ctx.needs_input_grad[2]
+        gf = torch.empty_like(f) if need_f else None
+        gw = torch.empty_like(wts) if need_w else None
+        gb = torch.empty(Cout, dtype=torch.float32, device=dev) if need_b else None
+        needs = (1 if need_f else 0) | (2 if need_w else 0) | (4 if need_b else 0)
+        if needs:
+            edges = offsets = None
+            if need_f and N > 0 and M > 0 and H > 0:
+                edges, offsets = inverted_index(nb, N)
+            with torch.cuda.device(dev):
+                ws = _lib.workspace(dev, L.gr_kpconv_backward_workspace_bytes(N, M, H, Cin, Cout, K, needs, ctx.chunk_rows))
+                _lib.check(L.gr_kpconv_backward(_lib.ptr(f), _lib.ptr(q), _lib.ptr(s), _lib.ptr(nb), N, M, H, Cin, Cout,
+                                                _lib.ptr(kp), K, _lib.ptr(wts), ctx.sigma, ctx.inf, _lib.ptr(go),
+                                                _lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(gf), _lib.ptr(gw), _lib.ptr(gb),
+                                                ctx.chunk_rows, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return gf, gw, gb, None, None, None, None, None, None, None
+
+
+class _PoolFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, nb, mode):
+        x = x.contiguous()
+        ctx.save_for_backward(x, nb)
+        ctx.mode = mode
+        return _pool_forward(x, nb, mode)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, nb = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        L = _lib.lib()
+        dev = x.device
+        N, C = x.shape
+        M, H = nb.shape
+        go = grad_out.to(torch.float32).contiguous()
+        gx = torch.empty_like(x)
+        edges, offsets = inverted_index(nb, N, first_column_only=ctx.mode == 1)
+        with torch.cuda.device(dev):
+            ws = _lib.workspace(dev, M * C * 4 + 256)
+            _lib.check(L.gr_neighbor_pool_backward(_lib.ptr(x), N, C, _lib.ptr(nb), M, H, ctx.mode, _lib.ptr(go),
+                                                   _lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(gx), _lib.ptr(ws),
+                                                   ws.numel(), _lib.stream_ptr(dev)))
+        return gx, None, None
+
+
+def _no_point_grad(**points):
+    for name, t in points.items():
+        if t.requires_grad:
+            raise ValueError(f"{name} requires grad, but the HIP KPConv has no gradient with respect to the points")
 
 
 class KPConv(nn.Module):
@@ -74,56 +232,79 @@ class KPConv(nn.Module):
             self._kernel_points_ready = True
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
-    @torch.no_grad()
     def forward(self, s_feats, q_points, s_points, neighbor_indices):
         if not self._kernel_points_ready:
             raise RuntimeError("KPConv.kernel_points is uninitialised: no stored disposition for kernel_size=%d; pass "
                                "kernel_points= or load a state dict that carries them" % self.kernel_size)
+        if differentiable_active():
+            return self._forward_differentiable(s_feats, q_points, s_points, neighbor_indices)
+        with torch.no_grad():
+            dev = _lib.require_gpu()
+            out_device = s_feats.device
+            f = _f32(s_feats, dev)
+            dev = f.device
+            q, s = _f32(q_points, dev), _f32(s_points, dev)
+            nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
+            kp = _f32(self.kernel_points, dev)
+            wts = _f32(self.weights.detach(), dev)
+            b = None if self.bias is None else _f32(self.bias.detach(), dev)
+            out = _kpconv_forward(f, q, s, nb, kp, wts, b, self.sigma, self.inf)
+            return out if out_device.type == "cuda" else out.to(out_device)
+
+    def _forward_differentiable(self, s_feats, q_points, s_points, neighbor_indices):
+        """The same kernels through one autograd Function; the conversions around it are torch ops with their own grad."""
+        _no_point_grad(q_points=q_points, s_points=s_points)
         dev = _lib.require_gpu()
-        L = _lib.lib()
         out_device = s_feats.device
         f = _f32(s_feats, dev)
         dev = f.device
         q, s = _f32(q_points, dev), _f32(s_points, dev)
         nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
         kp = _f32(self.kernel_points, dev)
-        wts = _f32(self.weights.detach(), dev)
-        b = None if self.bias is None else _f32(self.bias.detach(), dev)
-        N, Cin = f.shape
-        M, H = nb.shape
-        K, _, Cout = wts.shape
-        out = torch.empty((M, Cout), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_kpconv_workspace_bytes(N, M, K, Cin))
-            _lib.check(L.gr_kpconv_forward(_lib.ptr(f), _lib.ptr(q), _lib.ptr(s), _lib.ptr(nb), N, M, H, Cin, Cout,
-                                           _lib.ptr(kp), K, _lib.ptr(wts), _lib.ptr(b), float(self.sigma),
-                                           float(self.inf), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                           _lib.stream_ptr(dev)))
+        wts = _f32(self.weights, dev)
+        b = None if self.bias is None else _f32(self.bias, dev)
+        out = _KPConvFunction.apply(f, wts, b, q, s, nb, kp, float(self.sigma), float(self.inf), _mode.state[1])
         return out if out_device.type == "cuda" else out.to(out_device)
 
 
-def _pool(x, neighbor_indices, mode):
-    dev = _lib.require_gpu()
+def _pool_forward(xx, nb, mode):
+    """gr_neighbor_pool on a float32 contiguous tensor and int64 indices of one GPU."""
     L = _lib.lib()
-    out_device = x.device
-    xx = _f32(x, dev)
     dev = xx.device
-    nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
     N, C = xx.shape
     M, H = nb.shape
     out = torch.empty((M, C), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         _lib.check(L.gr_neighbor_pool(_lib.ptr(xx), N, C, _lib.ptr(nb), M, H, mode, _lib.ptr(out), _lib.stream_ptr(dev)))
+    return out
+
+
+def _pool(x, neighbor_indices, mode):
+    dev = _lib.require_gpu()
+    out_device = x.device
+    xx = _f32(x, dev)
+    dev = xx.device
+    nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
+    if differentiable_active():
+        out = _PoolFunction.apply(xx, nb, mode)
+    else:
+        with torch.no_grad():
+            out = _pool_forward(xx, nb, mode)
     return out if out_device.type == "cuda" else out.to(out_device)
 
 
-@torch.no_grad()
 def maxpool(x, neighbor_indices):
-    """kpconv/functional.py:54-67."""
-    return _pool(x, neighbor_indices, 0)
+    """kpconv/functional.py:54-67.  Inside `differentiable()` the gradient goes to the neighbour row that attained the
+    maximum (the lowest column on a tie; dropped where the zero shadow row won)."""
+    if differentiable_active():
+        return _pool(x, neighbor_indices, 0)
+    with torch.no_grad():
+        return _pool(x, neighbor_indices, 0)
 
 
-@torch.no_grad()
 def nearest_upsample(x, upsample_indices):
     """kpconv/functional.py:6-22 (only the first neighbour column is used)."""
-    return _pool(x, upsample_indices, 1)
+    if differentiable_active():
+        return _pool(x, upsample_indices, 1)
+    with torch.no_grad():
+        return _pool(x, upsample_indices, 1)

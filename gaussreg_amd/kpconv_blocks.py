@@ -1,4 +1,4 @@
-"""Mirror of geotransformer/modules/kpconv/modules.py (inference): the blocks KPConvFPN is assembled from
+"""Mirror of geotransformer/modules/kpconv/modules.py (inference; trainable inside `kpconv.differentiable()`): the blocks KPConvFPN is assembled from
 (backbone.py:95-162), with the HIP KPConv / maxpool / nearest_upsample / GroupNorm inside.  Sub-module names and parameter
 shapes follow the reference so its checkpoints load key for key (`KPConv.weights`, `norm.norm.weight`, `mlp.weight`, ...).
 nn.Linear stays the stock PyTorch-ROCm layer (rocBLAS), as in the reference."""
@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .kpconv import KPConv, maxpool, nearest_upsample
+from .kpconv import KPConv, differentiable_active, maxpool, nearest_upsample
 
 
 import contextlib
@@ -45,6 +45,9 @@ class GroupNorm(nn.Module):
         """`negative_slope`: fuse the LeakyReLU that follows the norm in every block (None: plain GroupNorm).
         `residual` (same shape as x): added between the norm and the activation -- the tail of a residual block."""
         c = self.num_channels
+        if differentiable_active() and getattr(_segments, "table", None):
+            raise NotImplementedError("norm_segments inside differentiable(): the torch GroupNorm that carries the gradient "
+                                      "has no segments; train one pair per pass")
         hip_ok = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and not torch.is_grad_enabled() and c % 4 == 0
                   and ((c // 4 <= 256 and 256 % (c // 4) == 0) or (c // 4) % 256 == 0) and self.num_groups <= 64)
         if not hip_ok:
@@ -220,8 +223,18 @@ class KPConvFPN(nn.Module):
         self.decoder3 = UnaryBlock(C * 24, C * 8, g)
         self.decoder2 = LastUnaryBlock(C * 12, output_dim)
 
-    @torch.no_grad()
     def forward(self, feats, data_dict):
+        """Inference (grad off) by default; inside `kpconv.differentiable()` with grad mode on, the whole backbone is
+        differentiable: HIP backward for KPConv / maxpool / nearest_upsample, torch autograd for the other layers."""
+        if differentiable_active():
+            if getattr(_segments, "table", None):
+                raise NotImplementedError("norm_segments inside differentiable(): the torch GroupNorm that carries the "
+                                          "gradient has no segments; train one pair per pass")
+            return self._forward(feats, data_dict)
+        with torch.no_grad():
+            return self._forward(feats, data_dict)
+
+    def _forward(self, feats, data_dict):
         pts, nb, sub, up = data_dict['points'], data_dict['neighbors'], data_dict['subsampling'], data_dict['upsampling']
         feats_list = []
         f1 = self.encoder1_2(self.encoder1_1(feats, pts[0], pts[0], nb[0]), pts[0], pts[0], nb[0])

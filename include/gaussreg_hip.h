@@ -402,6 +402,46 @@ int gr_gather_rows(const float* data, int64_t n, int64_t c, const int64_t* index
                    int* d_error_flag, void* stream);
 int gr_neighbor_pool(const float* x, int64_t n, int64_t c, const int64_t* neighbor_indices, int64_t m, int64_t h,
                      int mode, float* out, void* stream);
+/* gr_kpconv_backward: the gradients of gr_kpconv_forward with respect to s_feats (n,cin), weights (k,cin,cout) and bias
+ * (cout) for grad_out (m,cout, contiguous).  A null gradient pointer skips that gradient's work.  Points, kernel points and
+ * indices get no gradient.  No float atomics: the same device inputs give the same bits.
+ * inv_edges / inv_offsets (needed for grad_feats only): the inverted neighbour index -- inv_edges lists the valid entries
+ * of neighbor_indices as m * h_count + h, grouped by the support row they name and ascending inside a group; row r owns
+ * inv_edges[inv_offsets[r] .. inv_offsets[r + 1]) (n + 1 offsets).  m * h must stay below 2^31.
+ * The queries are processed in chunks (64 MB of WF and of gWF each; chunk_override > 0 sets the rows per chunk, for tests);
+ * chunk c adds into grad_feats / grad_weights after chunk c - 1, grad_weights is reduced over slabs of queries in
+ * ascending order.  gr_kpconv_backward_plan (host only) returns the bits below for the `needs` mask of gradients, or -1
+ * for sizes gr_kpconv_backward refuses; gr_kpconv_backward dispatches on that value. */
+enum {
+  GR_KPB_NEED_FEATS = 1, GR_KPB_NEED_WEIGHTS = 2, GR_KPB_NEED_BIAS = 4, /* the `needs` mask */
+  GR_KPB_SUM_G16 = 0,          /* inverted sum: 16 lanes per support row (cin <= 16) */
+  GR_KPB_SUM_G32 = 1,          /* 32 lanes (cin <= 32) */
+  GR_KPB_SUM_G64 = 2,          /* a whole wave per support row */
+  GR_KPB_SUM_MASK = 3,
+  GR_KPB_SUM_MULTIPASS = 4,    /* cin > 64: a lane walks the row's list once per 64 channels */
+  GR_KPB_FEATS = 8,            /* grad_feats is computed (gWF product + inverted sum) */
+  GR_KPB_WEIGHTS = 16,         /* grad_weights is computed (WF recomputed + slab products + fold) */
+  GR_KPB_WEIGHTS_SLABS = 32,   /* ... over more than one slab of queries per chunk */
+  GR_KPB_BIAS = 64,            /* grad_bias is computed */
+  GR_KPB_CHUNKED = 128,        /* more than one chunk of queries */
+  GR_KPB_EMPTY = 256           /* m, n or h is 0: grad_feats and grad_weights are zeros */
+};
+int gr_kpconv_backward_plan(int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout, int64_t k, int needs,
+                            int64_t chunk_override);
+size_t gr_kpconv_backward_workspace_bytes(int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout, int64_t k, int needs,
+                                          int64_t chunk_override);
+int gr_kpconv_backward(const float* s_feats, const float* q_points, const float* s_points, const int64_t* neighbor_indices,
+                       int64_t n, int64_t m, int64_t h, int64_t cin, int64_t cout, const float* kernel_points, int64_t k,
+                       const float* weights, float sigma, float inf, const float* grad_out, const int64_t* inv_edges,
+                       const int64_t* inv_offsets, float* grad_feats, float* grad_weights, float* grad_bias,
+                       int64_t chunk_override, void* ws, size_t ws_bytes, void* stream);
+/* gr_neighbor_pool_backward: grad_x (n,c) of gr_neighbor_pool.  mode 0 (maxpool): grad_out[m,c] goes to the neighbour row
+ * that attained the maximum, the lowest h on a tie, nowhere if the zero shadow row won; ws holds m * c int32.  mode 1
+ * (nearest_upsample): grad_x[r] = sum of grad_out[m] over the m with neighbor_indices[m,0] == r.  The inverted index is as
+ * for gr_kpconv_backward -- over all valid entries for mode 0, over column 0 alone for mode 1. */
+int gr_neighbor_pool_backward(const float* x, int64_t n, int64_t c, const int64_t* neighbor_indices, int64_t m, int64_t h,
+                              int mode, const float* grad_out, const int64_t* inv_edges, const int64_t* inv_offsets,
+                              float* grad_x, void* ws, size_t ws_bytes, void* stream);
 /* gr_group_norm: geotransformer/modules/kpconv/modules.py:32-50 GroupNorm.forward on the (N, C) matrix itself (the
  * reference transposes to (1, C, N) for nn.GroupNorm): statistics per group of C / groups channels over all n rows, biased
  * variance, y = (x - mean) / sqrt(var + eps) * gamma + beta, then LeakyReLU(negative_slope) -- pass 1.0f for none (the
