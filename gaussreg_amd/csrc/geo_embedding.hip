@@ -15,11 +15,10 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace gr {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int GE_ROWS = 128;  // (n,m) pairs per workgroup
 constexpr int GE_COLS = 256;  // output channels per workgroup
@@ -111,6 +110,30 @@ __device__ __forceinline__ void ge_pair_indices(const float* __restrict__ pts, i
   }
 }
 
+// epilogue of a wave's 64 x 64 block at (row0, col0): (proj_d + b_d) + reduce_k(proj_a + b_a).  Both evaluations end here: the
+// fp32 and the bf16 32 x 32 MFMAs leave their results in the same C / D layout (mfma_tile.hpp).
+__device__ __forceinline__ void ge_epilogue(const f32x16 (&acc)[2][2], const f32x16 (&red)[2][2], int64_t row0, int col0, int lane,
+                                            int64_t total, int C, int k, int mean, const float* __restrict__ b_d,
+                                            const float* __restrict__ b_a, float* __restrict__ out) {
+  const float inv_k = k > 0 ? 1.0f / (float)k : 0.f;
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int gj = mfma_col(col0 + b * 32, lane);
+      if (gj >= C) continue;
+      const float bd = b_d[gj], ba = k > 0 ? b_a[gj] : 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t gi = mfma_row(row0 + a * 32, r, lane);
+        if (gi < total) {
+          const float av = k > 0 ? (mean ? (red[a][b][r] + (float)k * ba) * inv_k : red[a][b][r] + ba) : 0.f;
+          out[gi * C + gj] = (acc[a][b][r] + bd) + av;
+        }
+      }
+    }
+}
+
 __global__ __launch_bounds__(GE_T) void geo_embedding_kernel(
     const float* __restrict__ pts, int n, const int32_t* __restrict__ knn, int k, const float* __restrict__ w_d,
     const float* __restrict__ b_d, const float* __restrict__ w_a, const float* __restrict__ b_a,
@@ -128,12 +151,8 @@ __global__ __launch_bounds__(GE_T) void geo_embedding_kernel(
   __syncthreads();
 
   f32x16 acc[2][2], red[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f, red[a][b][r] = 0.f;
+  mfma_zero(acc);
+  mfma_zero(red);
 
   // staging registers: A = 128 rows x 8 frequencies (sin, cos) -> 2 per thread; B = 256 cols x 16 k -> 8 per thread
   constexpr int NA = GE_ROWS * (GE_K / 2) / GE_T, NB = GE_COLS * GE_K / GE_T, NF = GE_K / 2;
@@ -180,16 +199,7 @@ __global__ __launch_bounds__(GE_T) void geo_embedding_kernel(
     const int phase = s / slabs;
     const bool more = s + 1 < steps;
     if (more) gen((s + 1) / slabs, ((s + 1) % slabs) * GE_K);  // overlaps the MFMAs below
-#pragma unroll
-    for (int kk2 = 0; kk2 < GE_K; kk2 += 2) {
-      const int kk = kk2 + (lane >> 5);
-      const float a0 = sa[buf][wi + (lane & 31)][kk], a1 = sa[buf][wi + 32 + (lane & 31)][kk];
-      const float b0 = sb[buf][wj + (lane & 31)][kk], b1 = sb[buf][wj + 32 + (lane & 31)][kk];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    mfma_slab<GE_K>(acc, sa[buf], sb[buf], wi, wj, lane);
     if ((s + 1) % slabs == 0 && phase < k) {
       // one angular projection finished: fold it into the reduction over the k neighbours (geotransformer.py:65-68)
 #pragma unroll
@@ -209,24 +219,7 @@ __global__ __launch_bounds__(GE_T) void geo_embedding_kernel(
       buf ^= 1;
     }
   }
-  // ---- epilogue: (proj_d + b_d) + reduce_k(proj_a + b_a)
-  const float inv_k = k > 0 ? 1.0f / (float)k : 0.f;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int gj = j0 + wj + b * 32 + (lane & 31);
-      if (gj >= C) continue;
-      const float bd = b_d[gj], ba = k > 0 ? b_a[gj] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t gi = r0 + wi + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (gi < total) {
-          const float av = k > 0 ? (mean ? (red[a][b][r] + (float)k * ba) * inv_k : red[a][b][r] + ba) : 0.f;
-          out[gi * C + gj] = (acc[a][b][r] + bd) + av;
-        }
-      }
-    }
+  ge_epilogue(acc, red, r0 + wi, j0 + wj, lane, total, C, k, mean, b_d, b_a, out);
 }
 
 
@@ -316,12 +309,8 @@ __global__ __launch_bounds__(GE_T) void geo_embedding_split_kernel(
   const bool big = s_big != 0;
 
   f32x16 acc[2][2], red[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f, red[a][b][r] = 0.f;
+  mfma_zero(acc);
+  mfma_zero(red);
 
   // staging: A = 128 rows x 8 frequencies -> 2 (row, f) per thread, each (sin, cos) x 3 parts packed in three words;
   //          B = 3 planes x 256 cols x 16 k bf16 = 1536 16-byte chunks -> 3 per thread
@@ -431,23 +420,7 @@ __global__ __launch_bounds__(GE_T) void geo_embedding_split_kernel(
       __syncthreads();
     }
   }
-  const float inv_k = k > 0 ? 1.0f / (float)k : 0.f;
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int gj = j0 + wj + b * 32 + (lane & 31);
-      if (gj >= C) continue;
-      const float bd = b_d[gj], ba = k > 0 ? b_a[gj] : 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int64_t gi = r0 + wi + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        if (gi < total) {
-          const float av = k > 0 ? (mean ? (red[a][b][r] + (float)k * ba) * inv_k : red[a][b][r] + ba) : 0.f;
-          out[gi * C + gj] = (acc[a][b][r] + bd) + av;
-        }
-      }
-    }
+  ge_epilogue(acc, red, r0 + wi, j0 + wj, lane, total, C, k, mean, b_d, b_a, out);
 }
 
 }  // namespace

@@ -11,11 +11,11 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace gr {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int KP_MAX = 16;   // kernel points (config.py:84 kernel_size = 15)
 constexpr int KP_HMAX = 256; // neighbours per query staged at once
 
@@ -219,47 +219,16 @@ __global__ __launch_bounds__(256) void kp_gather_mfma_kernel(
   if (lane == 0) inv_num[m] = (float)max(cnt, 1);                         // :114 max(neighbor_num, 1)
 }
 
-constexpr int GT = 64, GK = 32, GLD = GK + 1;
-
-// C (M x N) = A (M x Kd, row-major) . B (Kd x N, row-major);  out = C / den[m] + bias[n]
+// C (M x N) = A (M x Kd, row-major) . B (Kd x N, row-major);  out = C / den[m] + bias[n]   (the 64 x 64 tile of mfma_tile.hpp)
 __global__ __launch_bounds__(256) void gemm_nn_kernel(const float* __restrict__ A, const float* __restrict__ B, int M,
                                                       int N, int Kd, const float* __restrict__ den,
                                                       const float* __restrict__ bias, float* __restrict__ out) {
-  __shared__ float sa[GT][GLD];
-  __shared__ float sb[GT][GLD];
-  const int i0 = blockIdx.y * GT, j0 = blockIdx.x * GT;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
-  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k0 = 0; k0 < Kd; k0 += GK) {
-    for (int e = tid; e < GT * GK; e += 256) {
-      const int r = e / GK, k = e % GK;   // A tile: coalesced along k
-      const int gi = i0 + r, gk = k0 + k;
-      sa[r][k] = (gi < M && gk < Kd) ? A[(int64_t)gi * Kd + gk] : 0.f;
-      const int kk = e / GT, j = e % GT;  // B tile: coalesced along j, stored transposed
-      const int gj = j0 + j, gkb = k0 + kk;
-      sb[j][kk] = (gj < N && gkb < Kd) ? B[(int64_t)gkb * N + gj] : 0.f;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < GK; k += 2) {
-      const float a = sa[wi + (lane & 31)][k + (lane >> 5)];
-      const float b = sb[wj + (lane & 31)][k + (lane >> 5)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int gi = i0 + wi + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const int gj = j0 + wj + (lane & 31);
-    if (gi < M && gj < N) {
-      float v = acc[r];
-      if (den) v = v / den[gi];          // kpconv.py:115
-      if (bias) v = v + bias[gj];        // :118-119
-      out[(int64_t)gi * N + gj] = v;
-    }
-  }
+  gemm64_tile<true, false, false>(A, Kd, B, N, M, N, 0, Kd, (const float*)nullptr, (const float*)nullptr,
+                                  [=](int gi, int gj, float v) {
+                                    if (den) v = v / den[gi];    // kpconv.py:115
+                                    if (bias) v = v + bias[gj];  // :118-119
+                                    out[(int64_t)gi * N + gj] = v;
+                                  });
 }
 
 // Larger tile for the layers that dominate the backbone (M >= 128, N >= 128): 128 x 128 x 16 block tile,
@@ -286,12 +255,7 @@ __global__ __launch_bounds__(256) void gemm_nn_big_kernel(const float* __restric
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wi = (w >> 1) * WM, wj = (w & 1) * WN;
   f32x16 acc[TA][TB];
-#pragma unroll
-  for (int a = 0; a < TA; ++a)
-#pragma unroll
-    for (int b = 0; b < TB; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  mfma_zero(acc);
   // staging: A tile BM rows x 16 k (coalesced along k: 16 threads per row), B tile 16 k x BN cols
   constexpr int NA = BM * BK / 256, NBv = BN * BK / 256;
   float ra[NA], rb[NBv];
@@ -369,19 +333,7 @@ __global__ __launch_bounds__(256) void gemm_nn_big_kernel(const float* __restric
   for (int k0 = 0; k0 < Kd; k0 += BK) {
     const bool more = k0 + BK < Kd;
     if (more) load(k0 + BK);  // in flight during the MFMAs below
-#pragma unroll
-    for (int k = 0; k < BK; k += 2) {
-      const int kk = k + (lane >> 5);
-      float av[TA], bv[TB];
-#pragma unroll
-      for (int a = 0; a < TA; ++a) av[a] = sa[buf][wi + a * 32 + (lane & 31)][kk];
-#pragma unroll
-      for (int b = 0; b < TB; ++b) bv[b] = sb[buf][wj + b * 32 + (lane & 31)][kk];
-#pragma unroll
-      for (int a = 0; a < TA; ++a)
-#pragma unroll
-        for (int b = 0; b < TB; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
+    mfma_slab<BK>(acc, sa[buf], sb[buf], wi, wj, lane);
     if (more) {
       store(buf ^ 1);
       __syncthreads();
@@ -394,8 +346,7 @@ __global__ __launch_bounds__(256) void gemm_nn_big_kernel(const float* __restric
     for (int b = 0; b < TB; ++b)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int gi = i0 + wi + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const int gj = j0 + wj + b * 32 + (lane & 31);
+        const int gi = mfma_row(i0 + wi + a * 32, r, lane), gj = mfma_col(j0 + wj + b * 32, lane);
         if (gi < M && gj < N) {
           float v = acc[a][b][r];
           if (den) v = v / den[gi];

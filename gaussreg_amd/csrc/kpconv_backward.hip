@@ -18,16 +18,15 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace gr {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int KPB_KMAX = 16;                     // kernel points, as the forward
 constexpr int64_t KPB_CHUNK_BYTES = 64ll << 20;  // WF and gWF of one chunk of queries, each
 constexpr int64_t KPB_PART_BYTES = 32ll << 20;   // grad_W partial products of one chunk
 constexpr int KPB_MAX_SLABS = 32;
-constexpr int GT = 64, GK = 32, GLD = GK + 1;
 
 // max(#{h : neighbour valid and flagged}, 1) per query: what the gather kernels leave in `num`, for the calls that skip them
 __global__ __launch_bounds__(256) void kpb_num_kernel(const int64_t* __restrict__ nbr, int N, int M, int H,
@@ -42,61 +41,17 @@ __global__ __launch_bounds__(256) void kpb_num_kernel(const int64_t* __restrict_
   num[m] = (float)max(cnt, 1);
 }
 
-// C (Mi x Nj) = A (Mi x Kd) . B (Kd x Nj) over the k range of slab blockIdx.z, 64 x 64 tile on MFMA 32x32x2.
-//   A(i,k) = A_KFAST ? A[i lda + k] : A[k lda + i]   (optionally / denA[i])
-//   B(k,j) = B_KFAST ? B[j ldb + k] : B[k ldb + j]   (optionally / denB[k])
-// The staging loops run along whichever index is contiguous in memory.
+// C (Mi x Nj) = A (Mi x Kd) . B (Kd x Nj) over the k range of slab blockIdx.z: the 64 x 64 tile of mfma_tile.hpp with the
+// operands divided while they are staged (A(i,k) / denA[i], B(k,j) / denB[k], each when given).
 template <bool A_KFAST, bool B_KFAST>
 __global__ __launch_bounds__(256) void kpb_gemm_kernel(const float* __restrict__ A, int64_t lda, const float* __restrict__ B,
                                                        int64_t ldb, int Mi, int Nj, int Kd, int kslab,
                                                        const float* __restrict__ denA, const float* __restrict__ denB,
                                                        float* __restrict__ out, int64_t ldo, int64_t slab_stride) {
-  __shared__ float sa[GT][GLD];
-  __shared__ float sb[GT][GLD];
-  const int i0 = blockIdx.y * GT, j0 = blockIdx.x * GT;
   const int kb = blockIdx.z * kslab, ke = min(Kd, kb + kslab);
   out += (int64_t)blockIdx.z * slab_stride;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int wi = (w >> 1) * 32, wj = (w & 1) * 32;
-  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int k0 = kb; k0 < ke; k0 += GK) {
-    for (int e = tid; e < GT * GK; e += 256) {
-      {
-        const int r = A_KFAST ? e / GK : e % GT, k = A_KFAST ? e % GK : e / GT;
-        const int gi = i0 + r, gk = k0 + k;
-        float v = 0.f;
-        if (gi < Mi && gk < ke) {
-          v = A_KFAST ? A[(int64_t)gi * lda + gk] : A[(int64_t)gk * lda + gi];
-          if (denA) v = v / denA[gi];
-        }
-        sa[r][k] = v;
-      }
-      {
-        const int r = B_KFAST ? e / GK : e % GT, k = B_KFAST ? e % GK : e / GT;
-        const int gj = j0 + r, gk = k0 + k;
-        float v = 0.f;
-        if (gj < Nj && gk < ke) {
-          v = B_KFAST ? B[(int64_t)gj * ldb + gk] : B[(int64_t)gk * ldb + gj];
-          if (denB) v = v / denB[gk];
-        }
-        sb[r][k] = v;
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < GK; k += 2) {
-      const float a = sa[wi + (lane & 31)][k + (lane >> 5)];
-      const float b = sb[wj + (lane & 31)][k + (lane >> 5)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
-    __syncthreads();
-  }
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int gi = i0 + wi + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const int gj = j0 + wj + (lane & 31);
-    if (gi < Mi && gj < Nj) out[(int64_t)gi * ldo + gj] = acc[r];
-  }
+  gemm64_tile<A_KFAST, B_KFAST, true>(A, lda, B, ldb, Mi, Nj, kb, ke, denA, denB,
+                                      [=](int gi, int gj, float v) { out[(int64_t)gi * ldo + gj] = v; });
 }
 
 // out[i] = (accumulate ? out[i] : 0) + ((p[0][i] + p[1][i]) + p[2][i]) + ...   -- the slabs in ascending order

@@ -13,11 +13,10 @@
 #include <vector>
 
 #include "common.hpp"
+#include "mfma_tile.hpp"
 
 namespace gr {
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 constexpr int PD_T = 64;   // output tile 64 x 64 per 256-thread block, 32 x 32 per wave
 constexpr int PD_K = 32;   // k-slab staged in LDS
@@ -44,8 +43,7 @@ __device__ __forceinline__ T* z_shift(T* p, size_t bytes) {  // (pointer arithme
 // PARTIAL sums of their output tile -- rs_part[tile column][row] = the row's sum over the tile's columns, cs_part[tile row]
 // [column] = the column's sum over the tile's rows -- and sums_finish_kernel adds a row's / column's partials in tile order:
 // fixed summation order, no float atomics, and nobody reads the matrix again for it (the two-kernel form read it twice).
-// v[a][b][r]: the wave's values in MFMA C/D layout (col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) inside the
-// 32 x 32 block (a, b)), zero outside the matrix.  WR x WC waves per workgroup; wr / wc = this wave's position; s_red: LDS
+// v[a][b][r]: the wave's values in MFMA C/D layout (mfma_tile.hpp) inside the 32 x 32 block (a, b), zero outside the matrix.  WR x WC waves per workgroup; wr / wc = this wave's position; s_red: LDS
 // scratch of (WR + WC) * T floats (T = 32 * max(A * WR, B * WC) = the tile edge), free when this is called.
 template <int A, int B, int WR, int WC>
 __device__ __forceinline__ void tile_partial_sums(const float (&v)[A][B][16], int wr, int wc, int lane, int tid, float* s_red,
@@ -65,7 +63,7 @@ __device__ __forceinline__ void tile_partial_sums(const float (&v)[A][B][16], in
       for (int b = 1; b < B; ++b) t += v[a][b][r];
 #pragma unroll
       for (int d = 16; d > 0; d >>= 1) t += __shfl_xor(t, d, WAVE);
-      if ((lane & 31) == 0) s_rows[wc * T + wr * 32 * A + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)] = t;
+      if ((lane & 31) == 0) s_rows[mfma_row(wc * T + wr * 32 * A + 32 * a, r, lane)] = t;
     }
   // columns: the lane's 16 A values, then the other half-wave's
 #pragma unroll
@@ -91,18 +89,15 @@ __device__ __forceinline__ void tile_partial_sums(const float (&v)[A][B][16], in
   }
 }
 
-// out[i][j] = epilogue(dist(x[xi[i]], y[yi[j]]));  xi / yi optional gather tables (nullptr = identity).
-// n_dev / m_dev (optional) hold the row / column counts on the device (after a compaction).
-template <int EPI>
-__global__ __launch_bounds__(256) void pairwise_kernel(
-    const float* __restrict__ x, const float* __restrict__ y, const int32_t* __restrict__ xi,
-    const int32_t* __restrict__ yi, int n, int m, const int32_t* __restrict__ nm_dev, int C,
-    int normalized, const float* __restrict__ x2, const float* __restrict__ y2,
-    float* __restrict__ out, int ld_out, const SpmStack* __restrict__ stack, size_t zstride, PdBatch bs,
-    float* __restrict__ rs_part, float* __restrict__ cs_part, int ld_rs, int ld_cs) {
-  __shared__ float sx[PD_T][PD_LD];
-  __shared__ float sy[PD_T][PD_LD];
-  if (stack) {  // x = y = the stacked features; the gather tables, counts and the output belong to pair blockIdx.z
+// What blockIdx.z works on.  Stack mode: x = y = the stacked features; the gather tables, counts and the output belong to pair
+// blockIdx.z.  Plain batch (no stack, gridDim.z > 1): matrix blockIdx.z.  nm_dev: the counts come from the device.
+__device__ __forceinline__ void pd_select_matrix(const float* __restrict__& x, const float* __restrict__& y,
+                                                 const int32_t* __restrict__& xi, const int32_t* __restrict__& yi, int& n, int& m,
+                                                 const int32_t* __restrict__& nm_dev, int C, const float* __restrict__& x2,
+                                                 const float* __restrict__& y2, float* __restrict__& out, int& ld_out,
+                                                 const SpmStack* __restrict__ stack, size_t zstride, const PdBatch& bs,
+                                                 float* __restrict__& rs_part, float* __restrict__& cs_part) {
+  if (stack) {
     const SpmStack P = stack[blockIdx.z];
     y = x + (int64_t)P.s0 * C;
     x = x + (int64_t)P.r0 * C;
@@ -122,11 +117,37 @@ __global__ __launch_bounds__(256) void pairwise_kernel(
     n = nm_dev[0];
     m = nm_dev[1];
   }
+}
+
+// one output element from its dot product; x2 / y2: where the squared norms of its row and column are (read when not normalized)
+template <int EPI>
+__device__ __forceinline__ float pd_distance(float xy, int normalized, const float* x2, const float* y2) {
+  float d;
+  if (normalized) d = 2.0f - 2.0f * xy;      // pairwise_distance.py:26
+  else d = (*x2 - 2.0f * xy) + *y2;          // pairwise_distance.py:30
+  d = fmaxf(d, 0.0f);                        // :31 clamp(min=0)
+  if (EPI == EPI_EXPNEG) d = expf(-d);       // superpoint_matching.py:37
+  return d;
+}
+
+// out[i][j] = epilogue(dist(x[xi[i]], y[yi[j]]));  xi / yi optional gather tables (nullptr = identity).
+// n_dev / m_dev (optional) hold the row / column counts on the device (after a compaction).
+template <int EPI>
+__global__ __launch_bounds__(256) void pairwise_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const int32_t* __restrict__ xi,
+    const int32_t* __restrict__ yi, int n, int m, const int32_t* __restrict__ nm_dev, int C,
+    int normalized, const float* __restrict__ x2, const float* __restrict__ y2,
+    float* __restrict__ out, int ld_out, const SpmStack* __restrict__ stack, size_t zstride, PdBatch bs,
+    float* __restrict__ rs_part, float* __restrict__ cs_part, int ld_rs, int ld_cs) {
+  __shared__ float sx[PD_T][PD_LD];
+  __shared__ float sy[PD_T][PD_LD];
+  pd_select_matrix(x, y, xi, yi, n, m, nm_dev, C, x2, y2, out, ld_out, stack, zstride, bs, rs_part, cs_part);
   const int i0 = blockIdx.y * PD_T, j0 = blockIdx.x * PD_T;
   if (i0 >= n || j0 >= m) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int wi = (w >> 1) * 32, wj = (w & 1) * 32;  // wave's 32x32 sub-tile
-  f32x16 acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  f32x16 acc[1][1];
+  mfma_zero(acc);
   // staging: element e of a 64 x 32 slab = (row e / 32, k e % 32); a thread owns eight of them, the same (row, k) pair of
   // every slab, so its row addresses are fixed for the whole k loop.  The loads of slab s + 1 are issued before the MFMAs of
   // slab s (registers) and land while they run: one global round trip per slab used to sit between two barriers with nothing
@@ -163,29 +184,16 @@ __global__ __launch_bounds__(256) void pairwise_kernel(
     }
     __syncthreads();
     if (k0 + PD_K < C) fetch(k0 + PD_K);
-#pragma unroll
-    for (int k = 0; k < PD_K; k += 2) {
-      // A[i = lane & 31][k = lane >> 5],  B[k = lane >> 5][j = lane & 31]
-      const float a = sx[wi + (lane & 31)][k + (lane >> 5)];
-      const float b = sy[wj + (lane & 31)][k + (lane >> 5)];
-      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0);
-    }
+    mfma_slab<PD_K>(acc, sx, sy, wi, wj, lane);
     __syncthreads();
   }
-  // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
   float vals[1][1][16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const int gi = i0 + wi + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-    const int gj = j0 + wj + (lane & 31);
+    const int gi = mfma_row(i0 + wi, r, lane), gj = mfma_col(j0 + wj, lane);
     vals[0][0][r] = 0.f;
     if (gi < n && gj < m) {
-      const float xy = acc[r];
-      float d;
-      if (normalized) d = 2.0f - 2.0f * xy;                    // pairwise_distance.py:26
-      else d = (x2[gi] - 2.0f * xy) + y2[gj];                   // pairwise_distance.py:30
-      d = fmaxf(d, 0.0f);                                       // :31 clamp(min=0)
-      if (EPI == EPI_EXPNEG) d = expf(-d);                      // superpoint_matching.py:37
+      const float d = pd_distance<EPI>(acc[0][0][r], normalized, x2 + gi, y2 + gj);
       out[(int64_t)gi * ld_out + gj] = d;
       vals[0][0][r] = d;
     }
@@ -217,26 +225,7 @@ __global__ __launch_bounds__(256, 2) void pairwise_big_kernel(
     float* __restrict__ rs_part, float* __restrict__ cs_part, int ld_rs, int ld_cs) {
   __shared__ float sx[2][PB_T][PB_LD];
   __shared__ float sy[2][PB_T][PB_LD];
-  if (stack) {
-    const SpmStack P = stack[blockIdx.z];
-    y = x + (int64_t)P.s0 * C;
-    x = x + (int64_t)P.r0 * C;
-    n = P.nr;
-    m = P.ns;
-    ld_out = P.ns;
-    const size_t zo = (size_t)blockIdx.z * zstride;
-    xi = z_shift(xi, zo), yi = z_shift(yi, zo), nm_dev = z_shift(nm_dev, zo), out = z_shift(out, zo);
-    rs_part = z_shift(rs_part, zo), cs_part = z_shift(cs_part, zo);
-  }
-  if (!stack && gridDim.z > 1) {  // plain batch: matrix blockIdx.z
-    const int64_t z = blockIdx.z;
-    x += z * bs.x, y += z * bs.y, out += z * bs.out;
-    if (x2) x2 += z * bs.x2, y2 += z * bs.y2;
-  }
-  if (nm_dev) {
-    n = nm_dev[0];
-    m = nm_dev[1];
-  }
+  pd_select_matrix(x, y, xi, yi, n, m, nm_dev, C, x2, y2, out, ld_out, stack, zstride, bs, rs_part, cs_part);
   const int i0 = blockIdx.y * PB_T, j0 = blockIdx.x * PB_T;
   if (i0 >= n || j0 >= m) return;
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -282,12 +271,7 @@ __global__ __launch_bounds__(256, 2) void pairwise_big_kernel(
     d[3] = v.w;
   };
   f32x16 acc[2][2];
-#pragma unroll
-  for (int a = 0; a < 2; ++a)
-#pragma unroll
-    for (int b = 0; b < 2; ++b)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+  mfma_zero(acc);
   float4 rx[2], ry[2];
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
@@ -311,17 +295,7 @@ __global__ __launch_bounds__(256, 2) void pairwise_big_kernel(
         ry[u] = fetch(yrow[u], yok[u], (sidx + 1) * PB_K);
       }
     }
-#pragma unroll
-    for (int k = 0; k < PB_K; k += 2) {
-      // A[i = lane & 31][k = lane >> 5],  B[k = lane >> 5][j = lane & 31]
-      const int kk = k + (lane >> 5), rr = lane & 31;
-      const float a0 = sx[cur][wi + rr][kk], a1 = sx[cur][wi + 32 + rr][kk];
-      const float b0 = sy[cur][wj + rr][kk], b1 = sy[cur][wj + 32 + rr][kk];
-      acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-      acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-      acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-      acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-    }
+    mfma_slab<PB_K>(acc, sx[cur], sy[cur], wi, wj, lane);
     if (more) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
@@ -331,33 +305,25 @@ __global__ __launch_bounds__(256, 2) void pairwise_big_kernel(
     }
     __syncthreads();
   }
-  // C/D layout: col = lane & 31, row = (reg & 3) + 8 * (reg >> 2) + 4 * (lane >> 5)
   // the squared norms of the lane's rows and columns, requested up front on clamped indices (one memory round trip)
   float xx[2][16], yy[2];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int gi = i0 + wi + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-      xx[a][r] = normalized ? 0.f : x2[min(gi, n - 1)];
-    }
+    for (int r = 0; r < 16; ++r)
+      xx[a][r] = normalized ? 0.f : x2[min(mfma_row(i0 + wi + 32 * a, r, lane), n - 1)];
 #pragma unroll
-  for (int b = 0; b < 2; ++b) yy[b] = normalized ? 0.f : y2[min(j0 + wj + 32 * b + (lane & 31), m - 1)];
+  for (int b = 0; b < 2; ++b) yy[b] = normalized ? 0.f : y2[min(mfma_col(j0 + wj + 32 * b, lane), m - 1)];
   float vals[2][2][16];
 #pragma unroll
   for (int a = 0; a < 2; ++a)
 #pragma unroll
     for (int b = 0; b < 2; ++b) {
-      const int gj = j0 + wj + 32 * b + (lane & 31);
+      const int gj = mfma_col(j0 + wj + 32 * b, lane);
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int gi = i0 + wi + 32 * a + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-        const float xy = acc[a][b][r];
-        float d;
-        if (normalized) d = 2.0f - 2.0f * xy;      // pairwise_distance.py:26
-        else d = (xx[a][r] - 2.0f * xy) + yy[b];   // pairwise_distance.py:30
-        d = fmaxf(d, 0.0f);                        // :31 clamp(min=0)
-        if (EPI == EPI_EXPNEG) d = expf(-d);       // superpoint_matching.py:37
+        const int gi = mfma_row(i0 + wi + 32 * a, r, lane);
+        const float d = pd_distance<EPI>(acc[a][b][r], normalized, &xx[a][r], &yy[b]);
         const bool in = gi < n && gj < m;
         if (in) out[(int64_t)gi * ld_out + gj] = d;
         vals[a][b][r] = in ? d : 0.f;
