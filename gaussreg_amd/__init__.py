@@ -7,3 +7,10 @@ Device side: hand-written HIP kernels for gfx950 behind the C ABI in include/gau
 There is no CPU fallback: every op raises if the HIP library or a GPU is missing.
 """
 __version__ = "0.1.0"
+
+
+def differentiable(chunk_rows=0):
+    """`with gaussreg_amd.differentiable():` -- the one switch that makes the KPConv backbone and the transformer stack
+    differentiable (gaussreg_amd.kpconv.differentiable; imported on use so that `import gaussreg_amd` stays light)."""
+    from .kpconv import differentiable as ctx
+    return ctx(chunk_rows)

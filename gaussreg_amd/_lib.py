@@ -148,6 +148,9 @@ SIGNATURES.update({
     "gr_geo_embedding_table": (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_i64, c_f32, c_void, c_void, c_void, c_void, c_void,
                                        c_i64, c_f32, c_f32, c_i64, c_int, c_void, c_void, c_size, c_void]),
     "gr_rpe_attention": (c_int, [c_void] * 9 + [c_i64] * 4 + [c_void, c_void, c_void]),
+    "gr_rpe_attention_backward_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
+    "gr_rpe_attention_backward_max_keys": (c_i64, [c_i64, c_i64]),
+    "gr_rpe_attention_backward": (c_int, [c_void] * 10 + [c_i64] * 4 + [c_void] * 6 + [c_void, c_size, c_void]),
     "gr_rpe_scores": (c_int, [c_void, c_void, c_void, c_i64, c_i64, c_i64, c_i64, c_void, c_void]),
     "gr_fps_workspace_bytes": (c_size, [c_i64, c_i64]),
     "gr_fps": (c_int, [c_void, c_i64p, c_i64p, c_i64p, c_i64, c_i64, c_void, c_void, c_size, c_void]),

@@ -1,12 +1,96 @@
 """Mirror of geotransformer/modules/geotransformer/geotransformer.py:9-73 (GeometricStructureEmbedding) and
-geotransformer/modules/transformer/positional_embedding.py:8-34 (SinusoidalPositionalEmbedding), inference only.
+geotransformer/modules/transformer/positional_embedding.py:8-34 (SinusoidalPositionalEmbedding).
 `forward` runs one fused HIP kernel per cloud (gaussreg_amd/csrc/geo_embedding.hip); state-dict keys are the
-reference's (`embedding.div_term` is a buffer, `proj_d.{weight,bias}`, `proj_a.{weight,bias}`)."""
+reference's (`embedding.div_term` is a buffer, `proj_d.{weight,bias}`, `proj_a.{weight,bias}`).
+
+Inference by default.  Inside `gaussreg_amd.kpconv.differentiable()` the forward is the same kernel (the same values) inside
+an autograd Function whose backward gives `proj_d` and `proj_a` their gradients: it recomputes the reference composition
+(indices, sinusoids, the two Linears, max / mean over angle_k) in torch, a chunk of rows at a time, and differentiates
+each chunk against its rows of the upstream (N,N,C) gradient.  Once per cloud and step, not once per layer.  Points get no
+gradient."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _lib
+from .kpconv import differentiable_active
+
+GRAD_CHUNK_BYTES = 32 << 20   # the backward's recomputation: (rows, N, angle_k, C) temporaries of about this size
+
+
+def _sinusoid(idx, div):
+    om = idx.unsqueeze(-1) * div
+    return torch.stack([torch.sin(om), torch.cos(om)], dim=-1).flatten(-2)     # (sin, cos) interleaved
+
+
+def _projection_grads(p, go, wd, bd, wa, ba, div, sigma_d, factor_a, k, mean):
+    """One cloud: p (N,3), go (N,N,C) -> the gradients of out = proj_d(sin(d_idx)) + reduce_k proj_a(sin(a_idx)) with
+    respect to (wd, bd, wa, ba), float32.  The indices follow geotransformer.py:38-53 with the kernel's neighbour rule
+    (ascending distance, lowest index first, the first entry dropped); rows are taken in ascending chunks.
+    The distances and the neighbour sets are RECOMPUTED here in torch fp32, not taken from the forward kernel: where two
+    neighbours are equidistant within fp32 rounding, or a point's distance to itself does not round to exactly 0, this may
+    pick another neighbour than the forward did and so differentiate a slightly different function (DESIGN.md 3.5.2,
+    Known gap 12).  On clouds whose distances are exact in fp32 both sides agree."""
+    N, C = p.shape[0], wd.shape[0]
+    leaves = [t.detach().clone().requires_grad_(True) for t in (wd, bd, wa, ba)]
+    grads = [torch.zeros_like(t) for t in leaves]
+    if N == 0:
+        return grads
+    with torch.no_grad():
+        x2 = (p * p).sum(1)
+        dist = (x2[:, None] - 2.0 * (p @ p.t()) + x2[None, :]).clamp_min(0.0).sqrt()
+        d_idx = dist / sigma_d
+        if k > 0:
+            knn = torch.sort(dist, dim=1, stable=True)[1][:, 1:k + 1]
+            ref = p[knn] - p[:, None, :]                                       # (N, k, 3)
+    rows = max(1, int(GRAD_CHUNK_BYTES // max(1, 3 * N * max(k, 1) * C * 4)))
+    for r0 in range(0, N, rows):
+        r1 = min(N, r0 + rows)
+        with torch.no_grad():
+            if k > 0:
+                anc = p[None, :, :] - p[r0:r1, None, :]                        # (rows, N, 3)
+                r = ref[r0:r1, None, :, :].expand(-1, N, -1, -1)
+                a = anc[:, :, None, :].expand(-1, -1, r.shape[2], -1)
+                sin = torch.linalg.norm(torch.cross(r, a, dim=-1), dim=-1)
+                cos = (r * a).sum(-1)
+                a_idx = torch.atan2(sin, cos) * factor_a                       # (rows, N, k)
+        with torch.enable_grad():
+            out = torch.nn.functional.linear(_sinusoid(d_idx[r0:r1], div), leaves[0], leaves[1])
+            if k > 0:
+                a_emb = torch.nn.functional.linear(_sinusoid(a_idx, div), leaves[2], leaves[3])
+                out = out + (a_emb.mean(dim=2) if mean else a_emb.max(dim=2)[0])
+            used = leaves if k > 0 else leaves[:2]
+            for g, d in zip(grads, torch.autograd.grad(out, used, go[r0:r1])):
+                g += d
+    return grads
+
+
+class _GeoEmbeddingFunction(torch.autograd.Function):
+    """Forward: the HIP kernel, whichever mode the module is in.  Backward: _projection_grads per cloud."""
+
+    @staticmethod
+    def forward(ctx, module, points, wd, bd, wa, ba):
+        out = module._forward_kernel(points)
+        ctx.module = module
+        ctx.save_for_backward(points, wd, bd, wa, ba)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        points, wd, bd, wa, ba = ctx.saved_tensors
+        m = ctx.module
+        dev = grad_out.device if grad_out.is_cuda else _lib.require_gpu()
+        f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        go, p, div = f(grad_out), f(points), f(m.embedding.div_term)
+        total = None
+        for b in range(p.shape[0]):
+            g = _projection_grads(p[b], go[b], f(wd), f(bd), f(wa), f(ba), div, float(m.sigma_d), float(m.factor_a),
+                                  int(m.angle_k), m.reduction_a == 'mean')
+            total = g if total is None else [t + x for t, x in zip(total, g)]
+        if total is None:
+            total = [torch.zeros_like(f(t)) for t in (wd, bd, wa, ba)]
+        grads = [t.to(device=w.device, dtype=w.dtype) for t, w in zip(total, (wd, bd, wa, ba))]
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
 
 class SinusoidalPositionalEmbedding(nn.Module):
@@ -74,9 +158,18 @@ class GeometricStructureEmbedding(nn.Module):
             self._tables = (stamp, table(self.proj_d, self.TABLE_X_MAX_D), table(self.proj_a, x_max_a))
         return self._tables[1], self._tables[2]
 
-    @torch.no_grad()
     def forward(self, points):
-        """points (B, N, 3) -> embeddings (B, N, N, hidden_dim), geotransformer.py:57-73."""
+        """points (B, N, 3) -> embeddings (B, N, N, hidden_dim), geotransformer.py:57-73.  Inside `differentiable()` the
+        result carries the gradient of proj_d / proj_a; points that require grad raise ValueError."""
+        if differentiable_active():
+            if points.requires_grad:
+                raise ValueError("points require grad, but the structure embedding has no gradient with respect to the points")
+            return _GeoEmbeddingFunction.apply(self, points, self.proj_d.weight, self.proj_d.bias, self.proj_a.weight,
+                                               self.proj_a.bias)
+        with torch.no_grad():
+            return self._forward_kernel(points)
+
+    def _forward_kernel(self, points):
         dev = _lib.require_gpu()
         L = _lib.lib()
         if points.dim() != 3 or points.shape[-1] != 3:

@@ -10,6 +10,7 @@ the reference's kernel optimiser, which is not reproduced: such a module must ge
 from a checkpoint and refuses to run until then.
 """
 import contextlib
+import functools
 import math
 import threading
 import weakref
@@ -53,10 +54,11 @@ _mode = threading.local()
 def differentiable(chunk_rows=0):
     """Inside this context, with grad mode on, `KPConv.forward`, `maxpool` and `nearest_upsample` run the same forward
     kernels as outside it and return tensors with a `grad_fn` whenever `s_feats` / `weights` / `bias` (or `x`) require
-    grad; `KPConvFPN.forward` no longer switches grad off.  Points, kernel points and indices get no gradient: a
-    `q_points` / `s_points` that requires grad raises ValueError.  Outside the context every call is inference, as
-    before.  Thread-local.  `chunk_rows` > 0 overrides the number of queries the KPConv backward processes per chunk
-    (tests)."""
+    grad; `KPConvFPN.forward` no longer switches grad off.  The transformer stack consults the same switch
+    (gaussreg_amd.transformer, .rpe_attention, .embedding): backbone and transformer become differentiable together.
+    Points, kernel points and indices get no gradient: a `q_points` / `s_points` that requires grad raises ValueError.
+    Outside the context every call is inference, as before.  Thread-local.  `chunk_rows` > 0 overrides the number of
+    queries the KPConv backward processes per chunk (tests)."""
     old = getattr(_mode, "state", None)
     _mode.state = (True, int(chunk_rows))
     try:
@@ -68,6 +70,18 @@ def differentiable(chunk_rows=0):
 def differentiable_active():
     """True inside `differentiable()` while grad mode is on."""
     return getattr(_mode, "state", None) is not None and torch.is_grad_enabled()
+
+
+def no_grad_unless_differentiable(fn):
+    """Decorator of the forwards that are inference-only outside the context: `@torch.no_grad()` unless
+    `differentiable_active()`, in which case the call runs with autograd as it is."""
+    @functools.wraps(fn)
+    def wrapper(*args, **kwargs):
+        if differentiable_active():
+            return fn(*args, **kwargs)
+        with torch.no_grad():
+            return fn(*args, **kwargs)
+    return wrapper
 
 
 _inv_cache = {}

@@ -1,4 +1,5 @@
-"""Mirror of geotransformer/modules/transformer/rpe_transformer.py:18-72 (RPEMultiHeadAttention), inference only.
+"""Mirror of geotransformer/modules/transformer/rpe_transformer.py:18-72 (RPEMultiHeadAttention) -- inference by default,
+with autograd (HIP backward, csrc/rpe_attention_backward.hip) inside `gaussreg_amd.kpconv.differentiable()`.
 
 The reference projects the (B,N,M,C) relative-position embedding through `proj_p` in every layer (77 GFLOP and a
 602 MB temporary at N=M=767, C=256) before contracting it with q.  The contraction is linear in the embedding, so it
@@ -7,12 +8,68 @@ input projections -- q k^T, the positional term, scaling, factors / weights / ma
 HIP kernel per batch element (gaussreg_amd/csrc/geo_embedding.hip: gr_rpe_attention): the embedding is streamed exactly
 once per layer and no (H,N,M) or (N,M,C) intermediate goes through HBM.  The projections (nn.Linear) and the tiny
 u = W_p^T q product stay torch ops.  State-dict keys are the reference's.
+
+Inside `differentiable()` the same projections run under torch autograd and the same forward kernel runs inside one
+autograd Function that keeps the embedding (by reference), u, the projected q / k / v and the probabilities; its backward is
+one gr_rpe_attention_backward call per element: a row pass that streams the embedding once more -- for grad_u and, when the
+embedding wants a gradient, grad_embed -- and a column pass for the key-side sums.  `attention_factors`, `key_weights` and
+masks get no gradient.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .kpconv import differentiable_active
+
+
+def _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H):
+    """gr_rpe_attention on the float32 contiguous tensors of one batch element -> hidden (N,C), scores (H,N,M)."""
+    L = _lib.lib()
+    dev = q2.device
+    (N, C), M = q2.shape, k2.shape[0]
+    scores = torch.empty((H, N, M), dtype=torch.float32, device=dev)
+    hidden = torch.empty((N, C), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(L.gr_rpe_attention(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2), _lib.ptr(k2), _lib.ptr(v2),
+                                      _lib.ptr(fac), _lib.ptr(kw), _lib.ptr(km), N, M, C, H, _lib.ptr(scores),
+                                      _lib.ptr(hidden), _lib.stream_ptr(dev)))
+    return hidden, scores
+
+
+class _RPEAttentionFunction(torch.autograd.Function):
+    """Forward: the inference kernel.  Backward: gr_rpe_attention_backward.  Saved: the inputs and the probabilities, all by
+    reference (the (N,M,C) embedding is the caller's tensor, not a copy)."""
+
+    @staticmethod
+    def forward(ctx, emb, u, add, q2, k2, v2, fac, kw, km, H):
+        hidden, scores = _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H)
+        ctx.save_for_backward(emb, u, q2, k2, v2, scores, fac, kw)
+        ctx.H = H
+        ctx.set_materialize_grads(False)       # an unused output hands over None: the kernel's null grad_scores path
+        return hidden, scores
+
+    @staticmethod
+    def backward(ctx, grad_hidden, grad_scores):
+        emb, u, q2, k2, v2, scores, fac, kw = ctx.saved_tensors
+        if grad_hidden is None and grad_scores is None:
+            return (None,) * 10
+        L = _lib.lib()
+        dev = q2.device
+        (N, C), M, H = q2.shape, k2.shape[0], ctx.H
+        gh = torch.zeros_like(q2) if grad_hidden is None else grad_hidden.to(torch.float32).contiguous()
+        gs = None if grad_scores is None else grad_scores.to(torch.float32).contiguous()
+        gq, gk, gv, gu = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2), torch.empty_like(u)
+        gadd = torch.empty((N, H), dtype=torch.float32, device=dev)
+        gemb = torch.empty_like(emb) if ctx.needs_input_grad[0] else None
+        with torch.cuda.device(dev):
+            ws = _lib.workspace(dev, L.gr_rpe_attention_backward_workspace_bytes(N, M, H))
+            _lib.check(L.gr_rpe_attention_backward(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(q2), _lib.ptr(k2), _lib.ptr(v2),
+                                                   _lib.ptr(scores), _lib.ptr(fac), _lib.ptr(kw), _lib.ptr(gh), _lib.ptr(gs),
+                                                   N, M, C, H, _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(gu),
+                                                   _lib.ptr(gadd), _lib.ptr(gemb), _lib.ptr(ws), ws.numel(),
+                                                   _lib.stream_ptr(dev)))
+        return gemb, gu, gadd, gq, gk, gv, None, None, None, None
 
 
 class RPEMultiHeadAttention(nn.Module):
@@ -29,7 +86,6 @@ class RPEMultiHeadAttention(nn.Module):
         self.proj_p = nn.Linear(self.d_model, self.d_model)
         self.dropout = nn.Identity() if dropout is None or dropout <= 0 else nn.Dropout(dropout)
 
-    @torch.no_grad()
     def forward(self, input_q, input_k, input_v, embed_qk, key_weights=None, key_masks=None, attention_factors=None,
                 lengths=None):
         """(B,N,C), (B,M,C), (B,M,C), (B,N,M,C) -> hidden_states (B,N,C), attention_scores (B,H,N,M).
@@ -37,7 +93,17 @@ class RPEMultiHeadAttention(nn.Module):
         `lengths` (not in the reference; a list of B ints, self-attention only): the batch is a padded stack of B clouds of
         different sizes -- element b has lengths[b] real rows, `embed_qk` is then a LIST of B tensors (n_b, n_b, C).  The
         fused kernel runs per element with its true size, so the real rows are exactly what the unpadded call returns;
-        padded rows of hidden_states are zero, attention_scores is None."""
+        padded rows of hidden_states are zero, attention_scores is None.
+
+        Inside `differentiable()` (grad mode on) the outputs carry a grad_fn; their values are those of inference."""
+        if differentiable_active():
+            return self._forward_differentiable(input_q, input_k, input_v, embed_qk, key_weights, key_masks,
+                                                attention_factors, lengths)
+        with torch.no_grad():
+            return self._forward_inference(input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors,
+                                           lengths)
+
+    def _forward_inference(self, input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors, lengths):
         if lengths is not None:
             return self._forward_ragged(input_q, input_k, input_v, embed_qk, lengths)
         dev = _lib.require_gpu()
@@ -66,7 +132,6 @@ class RPEMultiHeadAttention(nn.Module):
             scores = self.dropout(scores)  # inference: identity (the reference applies dropout to the scores before @ v)
         return hidden, scores
 
-
     def _project(self, xq, xk, xv):
         """The torch side of ONE batch element, (n,C) / (m,C) / (m,C) matrices: the three input projections (heads side by
         side), u = W_p[h]^T q[h] (n,H,C) and add = q[h] . b_p[h] (n,H).  Per element on purpose: the GEMM a BLAS call runs
@@ -82,7 +147,63 @@ class RPEMultiHeadAttention(nn.Module):
         add = torch.einsum('nhc,hc->nh', qh, self.proj_p.bias.view(H, ch)).contiguous()
         return q2, k2, v2, u, add
 
-    @torch.no_grad()
+    def _forward_differentiable(self, input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors,
+                                lengths):
+        """The same projections and the same kernel, the kernel inside _RPEAttentionFunction; everything around it is torch
+        ops with their own grad.  Refuses what the backward could not do, here and not at backward()."""
+        for name, t in (("key_weights", key_weights), ("attention_factors", attention_factors)):
+            if t is not None and t.requires_grad:
+                raise ValueError(f"{name} requires grad, but the HIP RPE attention has no gradient with respect to it")
+        if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
+            raise NotImplementedError("RPEMultiHeadAttention: dropout on the attention scores is not differentiable here")
+        _lib.require_gpu()
+        if not input_q.is_cuda:
+            raise RuntimeError("RPEMultiHeadAttention: inputs must live on the GPU")
+        B, N, C = input_q.shape
+        H = self.num_heads
+        max_keys = _lib.lib().gr_rpe_attention_backward_max_keys(C, H)
+        if lengths is not None:
+            if input_k.shape != input_q.shape or len(embed_qk) != B or len(lengths) != B:
+                raise ValueError("lengths: self-attention over a padded stack, one embedding per element")
+            rows = []
+            for b in range(B):
+                n = int(lengths[b])
+                emb = embed_qk[b]
+                if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
+                    raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
+                if n == 0:
+                    rows.append(torch.zeros((N, C), dtype=torch.float32, device=input_q.device))
+                    continue
+                self._check_backward_fits(n, H, max_keys)
+                q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
+                hid, _ = _RPEAttentionFunction.apply(emb, u, add, q2, k2, v2, None, None, None, H)   # its own scores tensor
+                rows.append(F.pad(hid, (0, 0, 0, N - n)))
+            return torch.stack(rows), None
+        M = input_k.shape[1]
+        self._check_backward_fits(M, H, max_keys)
+        emb = embed_qk.to(torch.float32).contiguous()
+        fac = None if attention_factors is None else attention_factors.to(torch.float32).contiguous()
+        kw = None if key_weights is None else key_weights.to(torch.float32).contiguous()
+        km = None if key_masks is None else key_masks.to(torch.uint8).contiguous()
+        hidden, scores = [], []
+        for b in range(B):
+            q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
+            # B = 1: a view, whose backward is a view of the (N,M,C) gradient (a select would copy it into zeros)
+            emb_b = emb.view(N, M, C) if B == 1 else emb[b]
+            hid, sc = _RPEAttentionFunction.apply(emb_b, u, add, q2, k2, v2, None if fac is None else fac[b],
+                                                  None if kw is None else kw[b], None if km is None else km[b], H)
+            hidden.append(hid)
+            scores.append(sc)
+        if B == 1:
+            return hidden[0].unsqueeze(0), scores[0].unsqueeze(0)
+        return torch.stack(hidden), torch.stack(scores)
+
+    @staticmethod
+    def _check_backward_fits(m, heads, max_keys):
+        if m > max_keys:
+            raise RuntimeError("gaussreg_hip: rpe_attention_backward: %d keys x %d heads do not fit in LDS (at most %d keys "
+                               "inside differentiable())" % (m, heads, max_keys))
+
     def _forward_ragged(self, input_q, input_k, input_v, embed_list, lengths):
         L = _lib.lib()
         dev = input_q.device

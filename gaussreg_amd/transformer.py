@@ -1,4 +1,5 @@
-"""Mirrors of the transformer stack GaussReg's coarse matcher runs on the superpoints, inference only:
+"""Mirrors of the transformer stack GaussReg's coarse matcher runs on the superpoints -- inference by default, trainable
+inside `gaussreg_amd.kpconv.differentiable()`:
 
   AttentionOutput            geotransformer/modules/transformer/output_layer.py:6-21
   MultiHeadAttention         geotransformer/modules/transformer/vanilla_transformer.py:15-69
@@ -15,12 +16,17 @@ that carry the cost are HIP: the structure embedding (gaussreg_amd.embedding, on
 self-attention with the relative-position term (gaussreg_amd.rpe_attention, one fused kernel per batch element).  The
 cross-attention has no (N,M,C) stream -- 767 x 767 x 256 is three small GEMMs and a softmax -- and stays on rocBLAS
 through torch, like the nn.Linear / nn.LayerNorm glue around both.
+
+Every forward here switches grad off unless `differentiable_active()`.  Inside the context the torch glue is differentiated
+by torch autograd, the RPE attention by its HIP backward (csrc/rpe_attention_backward.hip) and the structure embedding's
+two projections by a chunked torch recomputation (gaussreg_amd.embedding); the forward values are those of inference.
 """
 import torch
 import torch.nn as nn
 
 from . import _lib
 from .embedding import GeometricStructureEmbedding
+from .kpconv import no_grad_unless_differentiable
 from .rpe_attention import RPEMultiHeadAttention
 
 _ACTIVATIONS = {'ReLU': nn.ReLU, 'LeakyReLU': nn.LeakyReLU, 'ELU': nn.ELU, 'GELU': nn.GELU, 'Sigmoid': nn.Sigmoid,
@@ -53,7 +59,7 @@ class AttentionOutput(nn.Module):
         self.dropout = _dropout(dropout)
         self.norm = nn.LayerNorm(d_model)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_states):
         grown = self.squeeze(self.activation(self.expand(input_states)))
         return self.norm(input_states + self.dropout(grown))
@@ -72,7 +78,7 @@ class MultiHeadAttention(nn.Module):
         self.proj_v = nn.Linear(self.d_model, self.d_model)
         self.dropout = _dropout(dropout)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_q, input_k, input_v, key_weights=None, key_masks=None, attention_factors=None,
                 attention_masks=None):
         """(B,N,C), (B,M,C), (B,M,C) -> hidden_states (B,N,C), attention_scores (B,H,N,M)."""
@@ -104,7 +110,7 @@ class AttentionLayer(nn.Module):
         self.dropout = _dropout(dropout)
         self.norm = nn.LayerNorm(d_model)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_states, memory_states, memory_weights=None, memory_masks=None, attention_factors=None,
                 attention_masks=None):
         hidden, scores = self.attention(input_states, memory_states, memory_states, key_weights=memory_weights,
@@ -119,7 +125,7 @@ class TransformerLayer(nn.Module):
         self.attention = AttentionLayer(d_model, num_heads, dropout=dropout)
         self.output = AttentionOutput(d_model, dropout=dropout, activation_fn=activation_fn)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_states, memory_states, memory_weights=None, memory_masks=None, attention_factors=None,
                 attention_masks=None):
         hidden, scores = self.attention(input_states, memory_states, memory_weights=memory_weights,
@@ -136,7 +142,7 @@ class RPEAttentionLayer(nn.Module):
         self.dropout = _dropout(dropout)
         self.norm = nn.LayerNorm(d_model)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_states, memory_states, position_states, memory_weights=None, memory_masks=None,
                 attention_factors=None, lengths=None):
         hidden, scores = self.attention(input_states, memory_states, memory_states, position_states,
@@ -151,7 +157,7 @@ class RPETransformerLayer(nn.Module):
         self.attention = RPEAttentionLayer(d_model, num_heads, dropout=dropout)
         self.output = AttentionOutput(d_model, dropout=dropout, activation_fn=activation_fn)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, input_states, memory_states, position_states, memory_weights=None, memory_masks=None,
                 attention_factors=None, lengths=None):
         hidden, scores = self.attention(input_states, memory_states, position_states, memory_weights=memory_weights,
@@ -174,7 +180,7 @@ class RPEConditionalTransformer(nn.Module):
         self.return_attention_scores = return_attention_scores
         self.parallel = parallel
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, feats0, feats1, embeddings0, embeddings1, masks0=None, masks1=None, lengths0=None, lengths1=None):
         """lengths0 / lengths1 (not in the reference): a padded stack of clouds of different sizes -- the self blocks then
         take one (n_b, n_b, C) embedding per element (lists) and run every element at its true size (RPEMultiHeadAttention);
@@ -210,7 +216,7 @@ class GeometricTransformer(nn.Module):
                                                      activation_fn=activation_fn)
         self.out_proj = nn.Linear(hidden_dim, output_dim)
 
-    @torch.no_grad()
+    @no_grad_unless_differentiable
     def forward(self, ref_points, src_points, ref_feats, src_feats, ref_masks=None, src_masks=None, ref_lengths=None,
                 src_lengths=None):
         """(B,N,3), (B,M,3), (B,N,Cin), (B,M,Cin) -> (B,N,Cout), (B,M,Cout).
@@ -219,9 +225,9 @@ class GeometricTransformer(nn.Module):
         padding): several scene pairs of different sizes as one padded batch -- the structure embedding and the
         self-attention run per cloud at its true size (no padded point can become a neighbour or a key), the cross-attention
         masks the padding; the rows of the real superpoints are those of the pair alone up to GEMM summation order."""
-        if ref_lengths is not None:
-            ref_embeddings = [self.embedding(ref_points[b:b + 1, :n])[0] for b, n in enumerate(ref_lengths)]
-            src_embeddings = [self.embedding(src_points[b:b + 1, :n])[0] for b, n in enumerate(src_lengths)]
+        if ref_lengths is not None:   # squeeze(0), not [0]: a view whose backward is a view of the (n,n,C) gradient, not a copy
+            ref_embeddings = [self.embedding(ref_points[b:b + 1, :n]).squeeze(0) for b, n in enumerate(ref_lengths)]
+            src_embeddings = [self.embedding(src_points[b:b + 1, :n]).squeeze(0) for b, n in enumerate(src_lengths)]
         else:
             ref_embeddings = self.embedding(ref_points)
             src_embeddings = self.embedding(src_points)

@@ -607,6 +607,21 @@ int gr_rpe_scores(const float* embed, const float* u, const float* add, int64_t 
 int gr_rpe_attention(const float* embed, const float* u, const float* add, const float* q, const float* k, const float* v,
                      const float* attention_factors, const float* key_weights, const uint8_t* key_masks, int64_t n,
                      int64_t m, int64_t c, int64_t heads, float* out_scores, float* out_hidden, void* stream);
+/* gr_rpe_attention_backward: the gradient of gr_rpe_attention, two launches, no float atomics (two runs give the same
+ * bits).  Inputs as the forward took them plus `scores` (heads,n,m), the probabilities it returned (a masked key has
+ * probability exactly 0, so no mask is passed); upstream grad_hidden (n,c) and grad_scores (heads,n,m) or null.
+ * Outputs: grad_q (n,c), grad_k / grad_v (m,c), grad_u (n,heads,c), grad_add (n,heads) and grad_embed (n,m,c) or null
+ * (not wanted: the n*m*c write is skipped).  A row pass (one workgroup per query) reads the embedding exactly once and
+ * leaves dz (heads,n,m), the gradient of the raw scores, in `ws`; a column pass sums over the queries for grad_k / grad_v.
+ * n == 0 zeroes grad_k / grad_v; m == 0 is refused; more than gr_rpe_attention_backward_max_keys(c, heads) keys do not
+ * fit in LDS (the row pass needs 4 * (heads * m + 4 * (heads + 1) * c) bytes) and are refused.  Asynchronous. */
+size_t gr_rpe_attention_backward_workspace_bytes(int64_t n, int64_t m, int64_t heads);
+int64_t gr_rpe_attention_backward_max_keys(int64_t c, int64_t heads);
+int gr_rpe_attention_backward(const float* embed, const float* u, const float* q, const float* k, const float* v,
+                              const float* scores, const float* attention_factors, const float* key_weights,
+                              const float* grad_hidden, const float* grad_scores, int64_t n, int64_t m, int64_t c,
+                              int64_t heads, float* grad_q, float* grad_k, float* grad_v, float* grad_u, float* grad_add,
+                              float* grad_embed, void* ws, size_t ws_bytes, void* stream);
 size_t gr_fps_workspace_bytes(int64_t n, int64_t batch);
 int gr_fps(const float* points, const int64_t* h_lengths, const int64_t* h_num_samples,
            const int64_t* h_start_indices, int64_t n, int64_t batch, int64_t* out_indices, void* ws,
