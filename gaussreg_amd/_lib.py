@@ -1,43 +1,24 @@
-"""ctypes binding of libgaussreg_hip.so (include/gaussreg_hip.h).  Fails loudly."""
+"""ctypes binding of libgaussreg_hip.so.  Fails loudly.
+
+include/gaussreg_hip.h is the only description of the ABI: `parse_header` reads it at import (without loading the library)
+into SIGNATURES, name -> (restype, argtypes), and DEFINES, the integer `#define GR_*` constants.  Only the three structs
+that cross the boundary are mirrored by hand (they hold arrays).  A declaration the parser does not understand raises.
+
+`call` is the one way a wrapper enters the library: it turns tensors into device pointers after checking that they are
+contiguous and on the GPU of the call, appends workspace and stream, enters the device and checks the status.
+"""
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libgaussreg_hip.so")
+HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip.h")
 
 _lib = None
 
 c_void = ctypes.c_void_p
-c_i64 = ctypes.c_int64
 c_f32 = ctypes.c_float
-c_int = ctypes.c_int
-c_size = ctypes.c_size_t
-c_i64p = ctypes.POINTER(ctypes.c_int64)
-
-# name -> (restype, argtypes); must list every symbol include/gaussreg_hip.h declares
-SIGNATURES = {
-    "gr_last_error": (ctypes.c_char_p, []),
-    "gr_version": (c_int, []),
-    "gr_timing_enable": (None, [c_int]),
-    "gr_timing_reset": (None, []),
-    "gr_timing_read": (c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double), c_i64p]),
-    "gr_radius_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
-    "gr_radius_count": (c_int, [c_void, c_void, c_i64p, c_i64p, c_i64, c_i64, c_i64, c_f32, c_void, c_size,
-                                c_i64p, c_void]),
-    "gr_radius_count_cached": (c_int, [c_void, c_void, c_i64p, c_i64p, c_i64, c_i64, c_i64, c_f32, c_void, c_size,
-                                c_i64p, c_i64p, c_int, c_void]),
-    "gr_radius_fill": (c_int, [c_void, c_void, c_i64, c_i64, c_i64, c_f32, c_i64, c_i64p, c_void, c_void,
-                               c_size, c_void]),
-    "gr_radius_search": (c_int, [c_void, c_void, c_i64p, c_i64p, c_i64, c_i64, c_i64, c_f32, c_i64, c_void, c_void, c_size,
-                                 c_i64p, c_i64p, c_int, c_void]),
-    "gr_radius_search_mode": (c_int, [c_int]),
-    "gr_host_unordered_map_order": (c_int, [ctypes.POINTER(ctypes.c_uint64), c_i64, ctypes.POINTER(ctypes.c_int32)]),
-    "gr_hash_order_device_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_hash_order_device": (c_int, [c_void, c_i64p, c_i64, c_void, c_void, c_size, c_void]),
-    "gr_grid_subsample_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_grid_subsample": (c_int, [c_void, c_i64p, c_i64, c_i64, c_f32, c_int, c_void, c_i64p, c_i64p, c_void,
-                                  c_size, c_void]),
-}
 
 
 class RasterView(ctypes.Structure):
@@ -48,152 +29,10 @@ class RasterView(ctypes.Structure):
                 ("sh_degree", ctypes.c_int32), ("prefiltered", ctypes.c_int32), ("debug", ctypes.c_int32)]
 
 
-# The three backward entries share their argument list; the map gradients and the camera outputs are spliced in.
-_BWD_HEAD = ([c_i64, c_int] + [c_void] * 7 +                    # P, M, the seven inputs
-             [ctypes.POINTER(RasterView), c_int, c_void, c_size, c_void, c_size, c_i64p] +  # views, geom, bin, num_rendered
-             [c_void] * 3)                                      # final_T, n_contrib, dL_dcolor
-_BWD_MAPS = [c_void] * 2                                        # dL_ddepth, dL_dalpha
-_BWD_GRADS = [c_int] + [c_void] * 8                             # flags, the eight input gradients
-_BWD_CAMERA = [c_void] * 3                                      # dL_dviewmatrix, dL_dprojmatrix, dL_dcampos
-_BWD_TAIL = [c_void, c_size, c_void]                            # scratch, its size, stream
-
-SIGNATURES.update({
-    "gr_raster_geom_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "gr_raster_bin_bytes": (c_size, [c_i64, c_int, c_int, c_int]),
-    "gr_raster_debug_geom_layout": (c_int, [c_i64, c_int, c_int, c_int, c_void]),
-    "gr_raster_debug_bucket_cooldown": (c_int, [c_int]),
-    "gr_raster_preprocess": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void,
-                                                                     c_void, c_size, c_i64p, c_void]),
-    "gr_raster_render": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
-                                 c_void, c_void]),
-    "gr_raster_render_ex": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
-                                    c_void, c_int, c_void]),
-    "gr_raster_forward": (c_int, [c_i64, c_int] + [c_void] * 7 + [ctypes.POINTER(RasterView), c_int, c_void, c_void, c_size,
-                                  c_void, c_size, c_void, c_int, c_i64p, c_void]),
-    "gr_raster_forward_finish": (c_int, [c_i64p]),
-    "gr_raster_lds_atomics_lane_ordered": (c_int, []),
-    "gr_raster_ballot_ranking": (c_int, [c_int]),
-    "gr_raster_mark_visible": (c_int, [c_i64, c_void, ctypes.POINTER(c_f32), c_void, c_void]),
-    "gr_raster_render_keep": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
-                                      c_void, c_int, c_void]),
-    "gr_raster_backward_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
-    "gr_raster_backward": (c_int, _BWD_HEAD + _BWD_GRADS + _BWD_TAIL),
-    "gr_raster_render_aux": (c_int, [c_i64, ctypes.POINTER(RasterView), c_int, c_i64p, c_void, c_size, c_void, c_size,
-                                     c_void, c_void, c_void, c_void, c_int, c_void]),
-    "gr_raster_backward_aux_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p]),
-    "gr_raster_backward_aux": (c_int, _BWD_HEAD + _BWD_MAPS + _BWD_GRADS + _BWD_TAIL),
-    "gr_raster_backward_cam_bytes": (c_size, [c_i64, c_int, c_int, c_int, c_i64p, c_int]),
-    "gr_raster_backward_cam": (c_int, _BWD_HEAD + _BWD_MAPS + _BWD_GRADS + _BWD_CAMERA + _BWD_TAIL),
-})
-
-
-SIGNATURES.update({
-    "gr_sinkhorn_workspace_bytes": (c_size, [c_i64]),
-    "gr_sinkhorn": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_void, c_int, c_f32, c_int, c_void, c_void, c_size,
-                            c_void]),
-    "gr_kpconv_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_i64]),
-    "gr_kpconv_plan": (c_int, [c_i64] * 6 + [c_int]),
-    "gr_kpconv_forward": (c_int, [c_void] * 4 + [c_i64] * 5 + [c_void, c_i64, c_void, c_void, c_f32, c_f32, c_void,
-                                                            c_void, c_size, c_void]),
-    "gr_kpconv_backward_plan": (c_int, [c_i64] * 6 + [c_int, c_i64]),
-    "gr_kpconv_backward_workspace_bytes": (c_size, [c_i64] * 6 + [c_int, c_i64]),
-    "gr_kpconv_backward": (c_int, [c_void] * 4 + [c_i64] * 5 + [c_void, c_i64, c_void, c_f32, c_f32] + [c_void] * 6 +
-                           [c_i64, c_void, c_size, c_void]),
-    "gr_neighbor_pool_backward": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_int] + [c_void] * 4 +
-                                  [c_void, c_size, c_void]),
-    "gr_gather_rows": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_void, c_void, c_void]),
-    "gr_neighbor_pool": (c_int, [c_void, c_i64, c_i64, c_void, c_i64, c_i64, c_int, c_void, c_void]),
-    "gr_group_norm_workspace_bytes": (c_size, [c_i64]),
-    "gr_group_norm": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_f32, c_f32, c_void, c_void, c_size, c_void]),
-    "gr_group_norm_seg_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_group_norm_seg": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_f32, c_f32, c_void, c_void, c_i64, c_i64, c_void,
-                                  c_size, c_void]),
-    "gr_group_norm_res": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_f32, c_f32, c_void, c_void, c_void, c_i64, c_i64,
-                                  c_void, c_size, c_void]),
-    "gr_gs_fuse_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_gs_fuse": (c_int, [c_void, c_i64, c_void, c_i64, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double),
-                           ctypes.c_double, ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), ctypes.POINTER(c_f32), c_void,
-                           c_i64p, c_void, c_size, c_void]),
-    "gr_pairwise_distance_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_pairwise_distance": (c_int, [c_void, c_void, c_i64, c_i64, c_i64, c_int, c_void, c_void, c_size, c_void]),
-    "gr_fps_debug_force_fallback": (c_int, [c_int]),
-    "gr_fps_debug_bucket_sort": (c_int, [c_int]),
-    "gr_hash_order_debug_force_prescan": (c_int, [c_int]),
-    "gr_grid_subsample_debug_bucket_sort": (c_int, [c_int]),
-    "gr_standin_descriptors": (c_int, [c_void, c_i64, c_void, c_void, c_void, c_void, c_void, c_i64, c_f32, c_int, c_void, c_void]),
-    "gr_pairwise_distance_batch_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
-    "gr_pairwise_distance_batch": (c_int, [c_void, c_void, c_i64, c_i64, c_i64, c_i64, c_int, c_void, c_void, c_size, c_void]),
-    "gr_superpoint_matching_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_superpoint_matching": (c_int, [c_void, c_void, c_i64, c_i64, c_i64, c_void, c_void, c_int, c_int, c_void,
-                                       c_void, c_void, c_i64p, c_void, c_size, c_void]),
-    "gr_point_matching_workspace_bytes": (c_size, [c_i64]),
-    "gr_corr_matrix": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_int, c_int, c_f32, c_void, c_i64p,
-                               c_void, c_size, c_void]),
-    "gr_corr_matrix_exp": (c_int, [c_void, c_i64, c_i64, c_i64, c_void, c_void, c_int, c_int, c_f32, c_void, c_i64p,
-                                   c_void, c_size, c_void]),
-    "gr_corr_gather": (c_int, [c_void, c_i64, c_i64, c_i64] + [c_void] * 6 + [c_int] + [c_void] * 5 +
-                       [c_void, c_size, c_void]),
-    "gr_lgr_workspace_bytes": (c_size, [c_i64]),
-    "gr_lgr_register": (c_int, [c_void, c_void, c_void, c_i64, c_i64, c_void, c_f32, c_int, c_int, c_void, c_void,
-                                c_size, c_void]),
-    "gr_lgr_register_verify": (c_int, [c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_void, c_void, c_i64,
-                                       c_f32, c_int, c_int, c_void, c_void, c_size, c_void]),
-    "gr_ransac_sample_hash": (ctypes.c_uint32, [ctypes.c_uint32] * 4),
-    "gr_ransac_workspace_bytes": (c_size, [c_i64]),
-    "gr_ransac_similarity": (c_int, [c_void, c_void, c_i64, c_int, c_i64, ctypes.c_uint32, c_f32, c_int, c_int, c_void,
-                                     c_void, c_void, c_size, c_void]),
-    "gr_geo_embedding_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_geo_embedding": (c_int, [c_void, c_i64, c_void, c_void, c_void, c_void, c_void, c_i64, c_f32, c_f32, c_i64,
-                                 c_int, c_void, c_void, c_size, c_void]),
-    "gr_geo_embedding_table": (c_int, [c_void, c_i64, c_void, c_i64, c_void, c_i64, c_f32, c_void, c_void, c_void, c_void, c_void,
-                                       c_i64, c_f32, c_f32, c_i64, c_int, c_void, c_void, c_size, c_void]),
-    "gr_rpe_attention": (c_int, [c_void] * 9 + [c_i64] * 4 + [c_void, c_void, c_void]),
-    "gr_rpe_attention_backward_workspace_bytes": (c_size, [c_i64, c_i64, c_i64]),
-    "gr_rpe_attention_backward_max_keys": (c_i64, [c_i64, c_i64]),
-    "gr_rpe_attention_backward": (c_int, [c_void] * 10 + [c_i64] * 4 + [c_void] * 6 + [c_void, c_size, c_void]),
-    "gr_rpe_scores": (c_int, [c_void, c_void, c_void, c_i64, c_i64, c_i64, c_i64, c_void, c_void]),
-    "gr_fps_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_fps": (c_int, [c_void, c_i64p, c_i64p, c_i64p, c_i64, c_i64, c_void, c_void, c_size, c_void]),
-    "gr_point_to_node_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_point_to_node_batch_workspace_bytes": (c_size, [c_i64p, c_i64p, c_i64]),
-    "gr_point_to_node_partition_batch": (c_int, [c_void, c_i64p, c_void, c_i64p, c_i64, c_int, c_void, c_void, c_void, c_void,
-                                                 c_void, c_size, c_void]),
-    "gr_superpoint_matching_batch_workspace_bytes": (c_size, [c_i64p, c_i64]),
-    "gr_superpoint_matching_batch": (c_int, [c_void, c_i64p, c_i64, c_i64, c_void, c_int, c_int, c_void, c_void, c_void,
-                                             c_i64p, c_void, c_size, c_void]),
-    "gr_lgr_register_seg": (c_int, [c_void, c_void, c_void, c_i64, c_i64, c_void, c_void, c_i64, c_f32, c_int, c_int,
-                                    c_void, c_void, c_void, c_size, c_void]),
-    "gr_ransac_seg_workspace_bytes": (c_size, [c_i64, c_i64]),
-    "gr_ransac_similarity_seg": (c_int, [c_void, c_void, c_void, c_i64, c_int, c_i64, ctypes.c_uint32, c_f32, c_int, c_int,
-                                         c_void, c_void, c_void, c_void, c_size, c_void]),
-    "gr_point_to_node_partition": (c_int, [c_void, c_i64, c_void, c_i64, c_int, c_void, c_void, c_void, c_void,
-                                           c_void, c_size, c_void]),
-})
-
-
-SIGNATURES.update({
-    "gr_image_loss_workspace_bytes": (c_size, [c_int] * 4),
-    "gr_image_loss_keep_bytes": (c_size, [c_int] * 4),
-    "gr_image_loss_forward": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_f32, c_void, c_void, c_void, c_size,
-                                      c_void, c_size, c_void]),
-    "gr_image_loss_backward": (c_int, [c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_f32, c_void, c_size, c_void, c_void,
-                                       c_void, c_void, c_size, c_void]),
-})
-
-
 class GsAdamGroup(ctypes.Structure):
     """struct gr_gs_adam_group (include/gaussreg_hip.h)."""
     _fields_ = [("param", c_void), ("grad", c_void), ("exp_avg", c_void), ("exp_avg_sq", c_void),
                 ("lr", ctypes.c_double), ("K", ctypes.c_int32)]
-
-
-GS_ADAM_MAX_GROUPS = 8
-
-SIGNATURES.update({
-    "gr_gs_adam_step": (c_int, [ctypes.POINTER(GsAdamGroup), c_int, c_i64] + [ctypes.c_double] * 5 + [c_void, c_void, c_int,
-                                                                                                    c_void]),
-    "gr_gs_densify_stats": (c_int, [c_void, c_void, c_i64, c_int, c_void, c_void, c_void, c_void]),
-})
 
 
 class GsDensifyGroup(ctypes.Structure):
@@ -202,22 +41,67 @@ class GsDensifyGroup(ctypes.Structure):
                 ("src_exp_avg_sq", c_void), ("dst_exp_avg_sq", c_void), ("K", ctypes.c_int32), ("role", ctypes.c_int32)]
 
 
-GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = 0, 1, 2
-
-SIGNATURES.update({
-    "gr_gs_densify_plan_workspace_bytes": (c_size, [c_i64]),
-    "gr_gs_densify_plan": (c_int, [c_void] * 5 + [c_i64] + [ctypes.c_double] * 4 + [c_int, ctypes.c_double, c_void, c_void, c_void,
-                                                                                     c_i64p, c_void, c_size, c_void]),
-    "gr_gs_densify_apply": (c_int, [ctypes.POINTER(GsDensifyGroup), c_int, c_i64, c_i64] + [c_void] * 6),
-})
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64,
+            "size_t": ctypes.c_size_t, "float": ctypes.c_float, "double": ctypes.c_double}
+_POINTEES = set(_SCALARS) | {"void", "uint8_t", "uint64_t"}     # any pointer to these is a c_void_p
+_STRUCTS = {"gr_raster_view": RasterView, "gr_gs_adam_group": GsAdamGroup, "gr_gs_densify_group": GsDensifyGroup}
+_TYPE = r"(?:const\s+)?(\w+)"
 
 
-GS_KNN_MAX_K = 8
+def _ctype(base, star, where):
+    if star:
+        if base == "char":
+            return ctypes.c_char_p
+        if base in _STRUCTS:
+            return ctypes.POINTER(_STRUCTS[base])
+        if base in _POINTEES:
+            return ctypes.c_void_p
+    elif base in _SCALARS:
+        return _SCALARS[base]
+    raise ValueError(f"gaussreg_hip.h: type '{base}{star}' in {where} is outside the binding's vocabulary")
 
-SIGNATURES.update({
-    "gr_gs_knn_workspace_bytes": (c_size, [c_i64, c_int]),
-    "gr_gs_knn": (c_int, [c_void, c_i64, c_int, c_void, c_void, c_void, c_void, c_size, c_void]),
-})
+
+def parse_header(text):
+    """-> (signatures, defines) of a header in the form of include/gaussreg_hip.h: every statement outside comments,
+    preprocessor lines, struct typedefs and enums is `<ret> gr_name(<type> <name>, ...);`.  Anything else raises and
+    names the declaration."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    defines = {m.group(1): int(m.group(2)) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(GR_\w+)[ \t]+(-?\d+)[ \t]*$",
+                                                                  text, flags=re.M)}
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"\b(?:typedef\s+struct|enum)\b[^{};]*\{[^{}]*\}[^;]*;", "", text)
+    text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r"\1", text, flags=re.S)
+    signatures = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        m = re.fullmatch(r"(.+?)\b(gr_\w+) ?\((.*)\)", decl)
+        if m is None:
+            raise ValueError(f"gaussreg_hip.h: cannot parse the declaration '{decl}'")
+        ret, name, args = m.group(1).strip(), m.group(2), m.group(3).strip()
+        r = re.fullmatch(_TYPE + r"\s*(\*?)", ret)
+        if r is None:
+            raise ValueError(f"gaussreg_hip.h: cannot parse the return type '{ret}' of {name}")
+        restype = None if r.groups() == ("void", "") else _ctype(r.group(1), r.group(2), f"the return type of {name}")
+        argtypes = []
+        for arg in ([] if args in ("", "void") else args.split(",")):
+            a = re.fullmatch(_TYPE + r"(?:\s*(\*)\s*|\s+)\w+", arg.strip())
+            if a is None:
+                raise ValueError(f"gaussreg_hip.h: cannot parse the argument '{arg.strip()}' of {name}")
+            argtypes.append(_ctype(a.group(1), a.group(2) or "", f"argument '{arg.strip()}' of {name}"))
+        if name in signatures:
+            raise ValueError(f"gaussreg_hip.h: {name} is declared twice")
+        signatures[name] = (restype, argtypes)
+    return signatures, defines
+
+
+with open(HEADER_PATH) as _f:
+    SIGNATURES, DEFINES = parse_header(_f.read())
+
+GR_PENDING = DEFINES["GR_PENDING"]        # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
+GR_RETRY_FULL = DEFINES["GR_RETRY_FULL"]  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward
+GR_RETRY_BIN = DEFINES["GR_RETRY_BIN"]    # gr_raster_forward: bin buffer too small, call gr_raster_render_ex
+GS_ADAM_MAX_GROUPS = DEFINES["GR_GS_ADAM_MAX_GROUPS"]
+GS_KNN_MAX_K = DEFINES["GR_GS_KNN_MAX_K"]
+GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = (DEFINES["GR_GS_DENSIFY_" + r] for r in ("CARRIED", "XYZ", "SCALING"))
 
 
 class HipLibraryError(RuntimeError):
@@ -243,11 +127,6 @@ def lib():
             fn.argtypes = args
         _lib = L
     return _lib
-
-
-GR_PENDING = 2     # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
-GR_RETRY_FULL = 3  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward (depth >= 8192)
-GR_RETRY_BIN = 1   # include/gaussreg_hip.h: gr_raster_forward's "bin buffer too small, call gr_raster_render_ex" status
 
 
 def check(rc, allow=()):
@@ -301,7 +180,73 @@ def stream_ptr(device):
 
 
 def ptr(t):
+    """Unchecked address of any tensor: the rasterizer's per-frame path, and host tensors handed over on purpose."""
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+
+
+def device_ptr(t, dev, what, pos=None):
+    """Address of `t` for a kernel that runs on `dev` (None stays NULL): `t` must be contiguous and on that GPU.  The error
+    names `what`, and the argument position `pos` when there is one."""
+    if t is None:
+        return None
+    if t.is_cuda and t.device == dev and t.is_contiguous():
+        return t.data_ptr()
+    where = what if pos is None else f"{what}: argument {pos}"
+    if not t.is_contiguous():
+        raise HipLibraryError(f"{where}: the tensor is not contiguous")
+    raise HipLibraryError(f"{where}: the tensor is on {t.device}, the call runs on {dev}")
+
+
+def call(dev, name, *args, ws=None, allow=()):
+    """Run the entry point `name` on the GPU `dev`, on torch's current stream there, and check its status (`allow`: as
+    in `check`); -> the status.  Every tensor among `args` is passed as its device pointer (`device_ptr`: a tensor that
+    is elsewhere or strided raises before the device is touched); host memory is passed as ctypes objects, as it is.
+    The stream is appended as the last argument; with `ws`, (workspace, its size) go in front of it, where every entry
+    point with a workspace takes them: `ws` is a byte count -- the shared grow-only buffer of `workspace` -- or the
+    caller's own uint8 tensor, for a buffer that another call reads again."""
+    import torch
+    Tensor = torch.Tensor
+    argv = [device_ptr(a, dev, name, i) if isinstance(a, Tensor) else a for i, a in enumerate(args)]
+    if ws is not None:
+        if not isinstance(ws, Tensor):
+            ws = workspace(dev, ws)
+        argv += (device_ptr(ws, dev, name + ": workspace"), ws.numel())
+    fn = getattr(lib(), name)
+    with torch.cuda.device(dev):
+        return check(fn(*argv, torch.cuda.current_stream(dev).cuda_stream), allow)
+
+
+def to_device(t, dev, dtype=None, name=None, cast=True):
+    """`t` contiguous on a GPU: a CPU tensor moves to `dev` (None: the current GPU), a GPU tensor stays where it is.
+    `dtype`: cast to it, or with cast=False insist on it ("<name> must be a float tensor": the text of the reference's
+    checks)."""
+    if dtype is not None and not cast and t.dtype != dtype:
+        raise RuntimeError(f"{name} must be a float tensor" if name else "expected a float tensor")
+    if dev is None:
+        dev = require_gpu()
+    t = t if t.is_cuda else t.to(dev)
+    return (t if dtype is None else t.to(dtype)).contiguous()
+
+
+def to_device_bool(t, dev):
+    """A mask as contiguous bool on a GPU (moved like `to_device`); any other dtype counts as `t != 0`."""
+    import torch
+    return to_device(t if t.dtype == torch.bool else t != 0, dev)
+
+
+def like_input(outs, out_device):
+    """A tensor or a tuple of tensors back on the device the caller's input came from (GPU results stay where they are)."""
+    if out_device.type == "cuda":
+        return outs
+    return tuple(o.to(out_device) for o in outs) if isinstance(outs, (tuple, list)) else outs.to(out_device)
+
+
+def offsets(lengths):
+    """[0, l0, l0 + l1, ...]: the offsets of stacked segments from their lengths, as Python ints."""
+    off = [0]
+    for n in lengths:
+        off.append(off[-1] + int(n))
+    return off
 
 
 def host_i64(values):

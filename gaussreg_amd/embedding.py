@@ -175,7 +175,7 @@ class GeometricStructureEmbedding(nn.Module):
         if points.dim() != 3 or points.shape[-1] != 3:
             raise ValueError("points must be (B, N, 3)")
         out_device = points.device
-        p = (points if points.is_cuda else points.to(dev)).to(torch.float32).contiguous()
+        p = _lib.to_device(points, dev, torch.float32)
         dev = p.device
         B, N, _ = p.shape
         C = self.proj_d.weight.shape[0]
@@ -183,22 +183,14 @@ class GeometricStructureEmbedding(nn.Module):
         wd, bd, wa, ba, div = f(self.proj_d.weight), f(self.proj_d.bias), f(self.proj_a.weight), f(self.proj_a.bias), \
             f(self.embedding.div_term)
         out = torch.empty((B, N, N, C), dtype=torch.float32, device=dev)
-        if self.mode == "table" and C % 4 == 0:
+        table = self.mode == "table" and C % 4 == 0
+        # both entry points end in: weights, C, scales, angle_k, reduction flags, the element's output
+        tail = (wd, bd, wa, ba, div, C, float(self.sigma_d), float(self.factor_a), int(self.angle_k),
+                (1 if self.reduction_a == 'mean' else 0) | (2 if self.fp32_mfma and not table else 0))
+        if table:
             td, ta = self._function_tables(dev)
-            with torch.cuda.device(dev):
-                ws = _lib.workspace(dev, L.gr_geo_embedding_workspace_bytes(N, int(self.angle_k)))
-                for b in range(B):
-                    _lib.check(L.gr_geo_embedding_table(_lib.ptr(p[b]), N, _lib.ptr(td), td.shape[0], _lib.ptr(ta), ta.shape[0],
-                                                        float(self.TABLE_INV_H), _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(wa),
-                                                        _lib.ptr(ba), _lib.ptr(div), C, float(self.sigma_d), float(self.factor_a),
-                                                        int(self.angle_k), 1 if self.reduction_a == 'mean' else 0,
-                                                        _lib.ptr(out[b]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-            return out if out_device.type == "cuda" else out.to(out_device)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_geo_embedding_workspace_bytes(N, int(self.angle_k)))
-            for b in range(B):
-                _lib.check(L.gr_geo_embedding(_lib.ptr(p[b]), N, _lib.ptr(wd), _lib.ptr(bd), _lib.ptr(wa), _lib.ptr(ba),
-                                              _lib.ptr(div), C, float(self.sigma_d), float(self.factor_a),
-                                              int(self.angle_k), (1 if self.reduction_a == 'mean' else 0) | (2 if self.fp32_mfma else 0),
-                                              _lib.ptr(out[b]), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return out if out_device.type == "cuda" else out.to(out_device)
+            tail = (td, td.shape[0], ta, ta.shape[0], float(self.TABLE_INV_H)) + tail
+        nbytes = L.gr_geo_embedding_workspace_bytes(N, int(self.angle_k))
+        for b in range(B):
+            _lib.call(dev, "gr_geo_embedding_table" if table else "gr_geo_embedding", p[b], N, *tail, out[b], ws=nbytes)
+        return _lib.like_input(out, out_device)

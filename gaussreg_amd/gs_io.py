@@ -102,7 +102,6 @@ def sh_band_transforms(rotation):
 def gaussian_fuse_records(rec1, rec2, estimated_transform):
     """gs_fusion.py:231-262 on (N,62) record arrays / tensors -> fused (M,62) float32 CUDA tensor."""
     dev = _lib.require_gpu()
-    L = _lib.lib()
     r1 = torch.as_tensor(rec1, dtype=torch.float32).to(dev).contiguous()
     r2 = torch.as_tensor(rec2, dtype=torch.float32).to(dev).contiguous()
     # gr_gs_fuse fetches records as 16-byte vectors: a view that starts at an odd row (248-byte records) is copied
@@ -121,12 +120,9 @@ def gaussian_fuse_records(rec1, rec2, estimated_transform):
     n_out = ctypes.c_int64(0)
     dp = ctypes.POINTER(ctypes.c_double)
     fp = ctypes.POINTER(ctypes.c_float)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_gs_fuse_workspace_bytes(n1, n2))
-        _lib.check(L.gr_gs_fuse(_lib.ptr(r1), n1, _lib.ptr(r2), n2, rotation.ctypes.data_as(dp),
-                                translation.ctypes.data_as(dp), scale, t1.ctypes.data_as(fp), t2.ctypes.data_as(fp),
-                                t3.ctypes.data_as(fp), _lib.ptr(out), ctypes.byref(n_out), _lib.ptr(ws), ws.numel(),
-                                _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_gs_fuse", r1, n1, r2, n2, rotation.ctypes.data_as(dp), translation.ctypes.data_as(dp), scale,
+              t1.ctypes.data_as(fp), t2.ctypes.data_as(fp), t3.ctypes.data_as(fp), out, ctypes.byref(n_out),
+              ws=_lib.lib().gr_gs_fuse_workspace_bytes(n1, n2))
     return out[: n_out.value]
 
 

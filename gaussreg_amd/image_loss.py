@@ -54,18 +54,15 @@ class _ImageLoss(torch.autograd.Function):
         V, C, H, W = x.shape
         dev = x.device
         need_grad = ctx.needs_input_grad[0]
-        with torch.cuda.device(dev):
-            loss = torch.empty(V, dtype=torch.float32, device=dev)
-            terms = torch.empty(V, 3, dtype=torch.float32, device=dev)
-            keep_bytes = int(L.gr_image_loss_keep_bytes(V, C, H, W)) if need_grad else 0
-            keep = torch.empty(keep_bytes // 4, dtype=torch.float32, device=dev) if need_grad else None
-            ws_bytes = int(L.gr_image_loss_workspace_bytes(V, C, H, W))
-            if ws_bytes == 0:
-                raise ValueError(f"image loss: unsupported shape {(V, C, H, W)} (V * C <= 65535)")
-            ws = _lib.workspace(dev, ws_bytes)
-            _lib.check(L.gr_image_loss_forward(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), V, C, H, W,
-                                               ctypes.c_float(lambda_dssim), _lib.ptr(loss), _lib.ptr(terms), _lib.ptr(keep),
-                                               keep_bytes, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        loss = torch.empty(V, dtype=torch.float32, device=dev)
+        terms = torch.empty(V, 3, dtype=torch.float32, device=dev)
+        keep_bytes = int(L.gr_image_loss_keep_bytes(V, C, H, W)) if need_grad else 0
+        keep = torch.empty(keep_bytes // 4, dtype=torch.float32, device=dev) if need_grad else None
+        ws_bytes = int(L.gr_image_loss_workspace_bytes(V, C, H, W))
+        if ws_bytes == 0:
+            raise ValueError(f"image loss: unsupported shape {(V, C, H, W)} (V * C <= 65535)")
+        _lib.call(dev, "gr_image_loss_forward", x, target, weight, V, C, H, W, ctypes.c_float(lambda_dssim), loss, terms, keep,
+                  keep_bytes, ws=ws_bytes)
         ctx.lambda_dssim = lambda_dssim
         ctx.want_ssim = want_ssim
         ctx.has_weight = weight is not None
@@ -78,18 +75,15 @@ class _ImageLoss(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out, _grad_terms):
-        L = _lib.lib()
         x, target, terms, keep = ctx.saved_tensors[:4]
         weight = ctx.saved_tensors[4] if ctx.has_weight else None
         V, C, H, W = x.shape
         dev = x.device
         # loss_v = (1 - lambda) l1 + lambda (1 - ssim_mean): at lambda = 1, d ssim_mean = -d loss_v
         g = (-grad_out if ctx.want_ssim else grad_out).to(torch.float32).contiguous()
-        with torch.cuda.device(dev):
-            dx = torch.empty_like(x)
-            _lib.check(L.gr_image_loss_backward(_lib.ptr(x), _lib.ptr(target), _lib.ptr(weight), V, C, H, W,
-                                                ctypes.c_float(ctx.lambda_dssim), _lib.ptr(keep), keep.numel() * 4,
-                                                _lib.ptr(terms), _lib.ptr(g), _lib.ptr(dx), None, 0, _lib.stream_ptr(dev)))
+        dx = torch.empty_like(x)
+        _lib.call(dev, "gr_image_loss_backward", x, target, weight, V, C, H, W, ctypes.c_float(ctx.lambda_dssim), keep,
+                  keep.numel() * 4, terms, g, dx, None, 0)  # (no workspace: NULL, 0)
         return dx, None, None, None, None
 
 

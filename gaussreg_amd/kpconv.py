@@ -43,10 +43,6 @@ def load_kernels(radius, num_kpoints, dimension=3, fixed='center'):
     return np.matmul(radius * pts, R).astype(np.float32)
 
 
-def _f32(t, dev):
-    return (t if t.is_cuda else t.to(dev)).to(torch.float32).contiguous()
-
-
 _mode = threading.local()
 
 
@@ -126,18 +122,13 @@ def _inv_cache_drop(key, ref):
 
 def _kpconv_forward(f, q, s, nb, kp, wts, b, sigma, inf):
     """gr_kpconv_forward on float32 / int64 contiguous tensors of one GPU."""
-    L = _lib.lib()
     dev = f.device
     N, Cin = f.shape
     M, H = nb.shape
     K, _, Cout = wts.shape
     out = torch.empty((M, Cout), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_kpconv_workspace_bytes(N, M, K, Cin))
-        _lib.check(L.gr_kpconv_forward(_lib.ptr(f), _lib.ptr(q), _lib.ptr(s), _lib.ptr(nb), N, M, H, Cin, Cout,
-                                       _lib.ptr(kp), K, _lib.ptr(wts), _lib.ptr(b), float(sigma),
-                                       float(inf), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                       _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_kpconv_forward", f, q, s, nb, N, M, H, Cin, Cout, kp, K, wts, b, float(sigma), float(inf), out,
+              ws=_lib.lib().gr_kpconv_workspace_bytes(N, M, K, Cin))
     return out
 
 
@@ -155,7 +146,6 @@ class _KPConvFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         f, wts, q, s, nb, kp = ctx.saved_tensors
-        L = _lib.lib()
         dev = f.device
         N, Cin = f.shape
         M, H = nb.shape
@@ -171,12 +161,9 @@ class _KPConvFunction(torch.autograd.Function):
             edges = offsets = None
             if need_f and N > 0 and M > 0 and H > 0:
                 edges, offsets = inverted_index(nb, N)
-            with torch.cuda.device(dev):
-                ws = _lib.workspace(dev, L.gr_kpconv_backward_workspace_bytes(N, M, H, Cin, Cout, K, needs, ctx.chunk_rows))
-                _lib.check(L.gr_kpconv_backward(_lib.ptr(f), _lib.ptr(q), _lib.ptr(s), _lib.ptr(nb), N, M, H, Cin, Cout,
-                                                _lib.ptr(kp), K, _lib.ptr(wts), ctx.sigma, ctx.inf, _lib.ptr(go),
-                                                _lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(gf), _lib.ptr(gw), _lib.ptr(gb),
-                                                ctx.chunk_rows, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+            _lib.call(dev, "gr_kpconv_backward", f, q, s, nb, N, M, H, Cin, Cout, kp, K, wts, ctx.sigma, ctx.inf, go, edges,
+                      offsets, gf, gw, gb, ctx.chunk_rows,
+                      ws=_lib.lib().gr_kpconv_backward_workspace_bytes(N, M, H, Cin, Cout, K, needs, ctx.chunk_rows))
         return gf, gw, gb, None, None, None, None, None, None, None
 
 
@@ -193,18 +180,13 @@ class _PoolFunction(torch.autograd.Function):
         x, nb = ctx.saved_tensors
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        L = _lib.lib()
         dev = x.device
         N, C = x.shape
         M, H = nb.shape
         go = grad_out.to(torch.float32).contiguous()
         gx = torch.empty_like(x)
         edges, offsets = inverted_index(nb, N, first_column_only=ctx.mode == 1)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, M * C * 4 + 256)
-            _lib.check(L.gr_neighbor_pool_backward(_lib.ptr(x), N, C, _lib.ptr(nb), M, H, ctx.mode, _lib.ptr(go),
-                                                   _lib.ptr(edges), _lib.ptr(offsets), _lib.ptr(gx), _lib.ptr(ws),
-                                                   ws.numel(), _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_neighbor_pool_backward", x, N, C, nb, M, H, ctx.mode, go, edges, offsets, gx, ws=M * C * 4 + 256)
         return gx, None, None
 
 
@@ -255,48 +237,46 @@ class KPConv(nn.Module):
         with torch.no_grad():
             dev = _lib.require_gpu()
             out_device = s_feats.device
-            f = _f32(s_feats, dev)
+            f = _lib.to_device(s_feats, dev, torch.float32)
             dev = f.device
-            q, s = _f32(q_points, dev), _f32(s_points, dev)
+            q, s = _lib.to_device(q_points, dev, torch.float32), _lib.to_device(s_points, dev, torch.float32)
             nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
-            kp = _f32(self.kernel_points, dev)
-            wts = _f32(self.weights.detach(), dev)
-            b = None if self.bias is None else _f32(self.bias.detach(), dev)
+            kp = _lib.to_device(self.kernel_points, dev, torch.float32)
+            wts = _lib.to_device(self.weights.detach(), dev, torch.float32)
+            b = None if self.bias is None else _lib.to_device(self.bias.detach(), dev, torch.float32)
             out = _kpconv_forward(f, q, s, nb, kp, wts, b, self.sigma, self.inf)
-            return out if out_device.type == "cuda" else out.to(out_device)
+            return _lib.like_input(out, out_device)
 
     def _forward_differentiable(self, s_feats, q_points, s_points, neighbor_indices):
         """The same kernels through one autograd Function; the conversions around it are torch ops with their own grad."""
         _no_point_grad(q_points=q_points, s_points=s_points)
         dev = _lib.require_gpu()
         out_device = s_feats.device
-        f = _f32(s_feats, dev)
+        f = _lib.to_device(s_feats, dev, torch.float32)
         dev = f.device
-        q, s = _f32(q_points, dev), _f32(s_points, dev)
+        q, s = _lib.to_device(q_points, dev, torch.float32), _lib.to_device(s_points, dev, torch.float32)
         nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
-        kp = _f32(self.kernel_points, dev)
-        wts = _f32(self.weights, dev)
-        b = None if self.bias is None else _f32(self.bias, dev)
+        kp = _lib.to_device(self.kernel_points, dev, torch.float32)
+        wts = _lib.to_device(self.weights, dev, torch.float32)
+        b = None if self.bias is None else _lib.to_device(self.bias, dev, torch.float32)
         out = _KPConvFunction.apply(f, wts, b, q, s, nb, kp, float(self.sigma), float(self.inf), _mode.state[1])
-        return out if out_device.type == "cuda" else out.to(out_device)
+        return _lib.like_input(out, out_device)
 
 
 def _pool_forward(xx, nb, mode):
     """gr_neighbor_pool on a float32 contiguous tensor and int64 indices of one GPU."""
-    L = _lib.lib()
     dev = xx.device
     N, C = xx.shape
     M, H = nb.shape
     out = torch.empty((M, C), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.gr_neighbor_pool(_lib.ptr(xx), N, C, _lib.ptr(nb), M, H, mode, _lib.ptr(out), _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_neighbor_pool", xx, N, C, nb, M, H, mode, out)
     return out
 
 
 def _pool(x, neighbor_indices, mode):
     dev = _lib.require_gpu()
     out_device = x.device
-    xx = _f32(x, dev)
+    xx = _lib.to_device(x, dev, torch.float32)
     dev = xx.device
     nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
     if differentiable_active():
@@ -304,7 +284,7 @@ def _pool(x, neighbor_indices, mode):
     else:
         with torch.no_grad():
             out = _pool_forward(xx, nb, mode)
-    return out if out_device.type == "cuda" else out.to(out_device)
+    return _lib.like_input(out, out_device)
 
 
 def maxpool(x, neighbor_indices):

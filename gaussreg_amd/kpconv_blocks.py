@@ -62,39 +62,25 @@ class GroupNorm(nn.Module):
         dev = x.device
         table = getattr(_segments, "table", None)
         seg = table.get(x.shape[0]) if table else None
-        with torch.cuda.device(dev):
-            w, b = self.norm.weight, self.norm.bias
-            if residual is not None:
-                res = residual.reshape(x.shape).contiguous()
-                seg_off, max_rows = seg if seg is not None else (None, 0)
-                nseg = seg_off.numel() - 1 if seg is not None else 1
-                ws = _lib.workspace(dev, L.gr_group_norm_seg_workspace_bytes(self.num_groups, nseg))
-                _lib.check(L.gr_group_norm_res(_lib.ptr(x), x.shape[0], c, self.num_groups,
-                                               _lib.ptr(None if w is None else w.detach().contiguous()),
-                                               _lib.ptr(None if b is None else b.detach().contiguous()), float(self.norm.eps),
-                                               1.0 if negative_slope is None else float(negative_slope), _lib.ptr(res),
-                                               _lib.ptr(out), _lib.ptr(seg_off), nseg, int(max_rows), _lib.ptr(ws), ws.numel(),
-                                               _lib.stream_ptr(dev)))
-                # the reference squeezes the norm's output BEFORE the shortcut is added (modules.py:50, :217-222): for a
-                # single row the sum broadcasts back to the shortcut's (1, C)
-                return out.reshape(torch.broadcast_shapes(out.squeeze().shape, residual.shape))
-            if seg is not None:
-                seg_off, max_rows = seg
-                nseg = seg_off.numel() - 1
-                ws = _lib.workspace(dev, L.gr_group_norm_seg_workspace_bytes(self.num_groups, nseg))
-                _lib.check(L.gr_group_norm_seg(_lib.ptr(x), x.shape[0], c, self.num_groups,
-                                               _lib.ptr(None if w is None else w.detach().contiguous()),
-                                               _lib.ptr(None if b is None else b.detach().contiguous()), float(self.norm.eps),
-                                               1.0 if negative_slope is None else float(negative_slope), _lib.ptr(out),
-                                               _lib.ptr(seg_off), nseg, int(max_rows), _lib.ptr(ws), ws.numel(),
-                                               _lib.stream_ptr(dev)))
-                return out.squeeze()
-            ws = _lib.workspace(dev, L.gr_group_norm_workspace_bytes(self.num_groups))
-            _lib.check(L.gr_group_norm(_lib.ptr(x), x.shape[0], c, self.num_groups,
-                                       _lib.ptr(None if w is None else w.detach().contiguous()),
-                                       _lib.ptr(None if b is None else b.detach().contiguous()), float(self.norm.eps),
-                                       1.0 if negative_slope is None else float(negative_slope), _lib.ptr(out), _lib.ptr(ws),
-                                       ws.numel(), _lib.stream_ptr(dev)))
+        w, b = self.norm.weight, self.norm.bias
+        # x, groups, affine parameters, eps, slope: the head of all three entry points
+        head = (x, x.shape[0], c, self.num_groups, None if w is None else w.detach().contiguous(),
+                None if b is None else b.detach().contiguous(), float(self.norm.eps),
+                1.0 if negative_slope is None else float(negative_slope))
+        seg_off, max_rows = seg if seg is not None else (None, 0)
+        nseg = seg_off.numel() - 1 if seg is not None else 1
+        if residual is not None:
+            res = residual.reshape(x.shape).contiguous()
+            _lib.call(dev, "gr_group_norm_res", *head, res, out, seg_off, nseg, int(max_rows),
+                      ws=L.gr_group_norm_seg_workspace_bytes(self.num_groups, nseg))
+            # the reference squeezes the norm's output BEFORE the shortcut is added (modules.py:50, :217-222): for a
+            # single row the sum broadcasts back to the shortcut's (1, C)
+            return out.reshape(torch.broadcast_shapes(out.squeeze().shape, residual.shape))
+        if seg is not None:
+            _lib.call(dev, "gr_group_norm_seg", *head, out, seg_off, nseg, int(max_rows),
+                      ws=L.gr_group_norm_seg_workspace_bytes(self.num_groups, nseg))
+        else:
+            _lib.call(dev, "gr_group_norm", *head, out, ws=L.gr_group_norm_workspace_bytes(self.num_groups))
         return out.squeeze()
 
 

@@ -16,16 +16,7 @@ import torch.nn as nn
 from . import _lib
 
 
-def _f32c(t, dev):
-    if t.dtype != torch.float32:
-        raise RuntimeError("expected a float tensor")
-    return (t if t.is_cuda else t.to(dev)).contiguous()
-
-
-def _boolc(t, dev):
-    if t.dtype != torch.bool:
-        t = t != 0
-    return (t if t.is_cuda else t.to(dev)).contiguous()
+_F32 = dict(dtype=torch.float32, cast=False)  # _lib.to_device: these modules insist on float tensors, they do not cast
 
 
 class SuperPointMatching(nn.Module):
@@ -38,13 +29,12 @@ class SuperPointMatching(nn.Module):
     def forward(self, ref_feats, src_feats, ref_masks=None, src_masks=None):
         """-> (ref_corr_indices (k,) i64, src_corr_indices (k,) i64, corr_scores (k,) f32 descending)."""
         dev = _lib.require_gpu()
-        L = _lib.lib()
         out_device = ref_feats.device
-        rf = _f32c(ref_feats, dev)
+        rf = _lib.to_device(ref_feats, dev, **_F32)
         dev = rf.device
-        sf = _f32c(src_feats, dev)
-        rm = None if ref_masks is None else _boolc(ref_masks, dev)
-        sm = None if src_masks is None else _boolc(src_masks, dev)
+        sf = _lib.to_device(src_feats, dev, **_F32)
+        rm = None if ref_masks is None else _lib.to_device_bool(ref_masks, dev)
+        sm = None if src_masks is None else _lib.to_device_bool(src_masks, dev)
         nr, c = rf.shape
         ns = sf.shape[0]
         k = int(self.num_correspondences)
@@ -52,18 +42,10 @@ class SuperPointMatching(nn.Module):
         si = torch.empty((k,), dtype=torch.int64, device=dev)
         sc = torch.empty((k,), dtype=torch.float32, device=dev)
         n_out = ctypes.c_int64(0)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_superpoint_matching_workspace_bytes(nr, ns))
-            _lib.check(L.gr_superpoint_matching(_lib.ptr(rf), _lib.ptr(sf), nr, ns, c, _lib.ptr(rm), _lib.ptr(sm), k,
-                                                int(bool(self.dual_normalization)), _lib.ptr(ri), _lib.ptr(si),
-                                                _lib.ptr(sc), ctypes.byref(n_out), _lib.ptr(ws), ws.numel(),
-                                                _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_superpoint_matching", rf, sf, nr, ns, c, rm, sm, k, int(bool(self.dual_normalization)), ri, si, sc,
+                  ctypes.byref(n_out), ws=_lib.lib().gr_superpoint_matching_workspace_bytes(nr, ns))
         n = n_out.value
-        ri, si, sc = ri[:n], si[:n], sc[:n]
-        if out_device.type != "cuda":
-            ri, si, sc = ri.to(out_device), si.to(out_device), sc.to(out_device)
-        return ri, si, sc
-
+        return _lib.like_input((ri[:n], si[:n], sc[:n]), out_device)
 
     @torch.no_grad()
     def forward_batch(self, feats, node_lengths, masks=None):
@@ -72,13 +54,10 @@ class SuperPointMatching(nn.Module):
         (sum M,) likewise.  -> (ref_corr_indices (B, k), src_corr_indices (B, k), corr_scores (B, k), counts: list of B ints
         -- row b is valid up to counts[b]).  One host read-back for the whole batch."""
         dev = _lib.require_gpu()
-        L = _lib.lib()
-        f = _f32c(feats, dev)
+        f = _lib.to_device(feats, dev, **_F32)
         dev = f.device
-        m = None if masks is None else _boolc(masks, dev)
-        off = [0]
-        for n in node_lengths:
-            off.append(off[-1] + int(n))
+        m = None if masks is None else _lib.to_device_bool(masks, dev)
+        off = _lib.offsets(node_lengths)
         if len(off) % 2 != 1 or off[-1] != f.shape[0]:
             raise ValueError("node_lengths must list ref and src sizes of every pair and sum to feats.shape[0]")
         B = (len(off) - 1) // 2
@@ -88,11 +67,8 @@ class SuperPointMatching(nn.Module):
         sc = torch.zeros((B, k), dtype=torch.float32, device=dev)
         h_off = _lib.host_i64(off)
         h_n = _lib.host_i64([0] * B)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_superpoint_matching_batch_workspace_bytes(h_off, B))
-            _lib.check(L.gr_superpoint_matching_batch(_lib.ptr(f), h_off, B, f.shape[1], _lib.ptr(m), k,
-                                                      int(bool(self.dual_normalization)), _lib.ptr(ri), _lib.ptr(si),
-                                                      _lib.ptr(sc), h_n, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_superpoint_matching_batch", f, h_off, B, f.shape[1], m, k, int(bool(self.dual_normalization)),
+                  ri, si, sc, h_n, ws=_lib.lib().gr_superpoint_matching_batch_workspace_bytes(h_off, B))
         return ri, si, sc, [int(h_n[b]) for b in range(B)]
 
 
@@ -114,19 +90,17 @@ class PointMatching(nn.Module):
 
     def _corr(self, score_mat, ref_knn_masks, src_knn_masks, want_count, scores_are_exp=False):
         dev = _lib.require_gpu()
-        L = _lib.lib()
-        s = _f32c(score_mat, dev)
+        s = _lib.to_device(score_mat, dev, **_F32)
         dev = s.device
-        rm, sm = _boolc(ref_knn_masks, dev), _boolc(src_knn_masks, dev)
+        rm, sm = _lib.to_device_bool(ref_knn_masks, dev), _lib.to_device_bool(src_knn_masks, dev)
         B, K1, K2 = s.shape
         corr = torch.empty((B, K1, K2), dtype=torch.bool, device=dev)
         n = ctypes.c_int64(0)
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_point_matching_workspace_bytes(B))
-            fn = L.gr_corr_matrix_exp if scores_are_exp else L.gr_corr_matrix
-            _lib.check(fn(_lib.ptr(s), B, K1, K2, _lib.ptr(rm), _lib.ptr(sm), int(self.k),
-                          int(bool(self.mutual)), float(self.confidence_threshold), _lib.ptr(corr),
-                          ctypes.byref(n) if want_count else None, _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        # the workspace keeps the per-patch counts: gr_corr_gather and gr_lgr_register_* read them, so it goes back to the caller
+        ws = _lib.workspace(dev, _lib.lib().gr_point_matching_workspace_bytes(B))
+        _lib.call(dev, "gr_corr_matrix_exp" if scores_are_exp else "gr_corr_matrix", s, B, K1, K2, rm, sm, int(self.k),
+                  int(bool(self.mutual)), float(self.confidence_threshold), corr, ctypes.byref(n) if want_count else None,
+                  ws=ws)
         return s, corr, n.value, ws
 
     @torch.no_grad()
@@ -134,7 +108,7 @@ class PointMatching(nn.Module):
         """`score_mat` here is exp(log-scores), as in the reference call sites (point_matching.py:98,
         local_global_registration.py:211): it is thresholded as given (gr_corr_matrix_exp), no log/exp round trip."""
         s, corr, _, _ = self._corr(score_mat, ref_knn_masks, src_knn_masks, False, scores_are_exp=True)
-        return corr if score_mat.is_cuda else corr.to(score_mat.device)
+        return _lib.like_input(corr, score_mat.device)
 
     @torch.no_grad()
     def forward(self, ref_knn_points, src_knn_points, ref_knn_masks, src_knn_masks, ref_knn_indices, src_knn_indices,
@@ -142,27 +116,20 @@ class PointMatching(nn.Module):
         out_device = score_mat.device
         s, corr, n, ws = self._corr(score_mat, ref_knn_masks, src_knn_masks, True)
         dev = s.device
-        L = _lib.lib()
         B, K1, K2 = s.shape
-        rp, sp = _f32c(ref_knn_points, dev), _f32c(src_knn_points, dev)
+        rp, sp = _lib.to_device(ref_knn_points, dev, **_F32), _lib.to_device(src_knn_points, dev, **_F32)
         ri = ref_knn_indices.to(dev).contiguous()
         si = src_knn_indices.to(dev).contiguous()
-        gs = _f32c(global_scores, dev) if (self.use_global_score and global_scores is not None) else None
+        gs = _lib.to_device(global_scores, dev, **_F32) if (self.use_global_score and global_scores is not None) else None
         o_rp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_sp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_ri = torch.empty((n,), dtype=torch.int64, device=dev)
         o_si = torch.empty((n,), dtype=torch.int64, device=dev)
         o_sc = torch.empty((n,), dtype=torch.float32, device=dev)
         if n > 0:
-            with torch.cuda.device(dev):
-                _lib.check(L.gr_corr_gather(_lib.ptr(s), B, K1, K2, _lib.ptr(corr), _lib.ptr(rp), _lib.ptr(sp),
-                                            _lib.ptr(ri), _lib.ptr(si), _lib.ptr(gs), int(gs is not None),
-                                            _lib.ptr(o_rp), _lib.ptr(o_sp), _lib.ptr(o_ri), _lib.ptr(o_si),
-                                            _lib.ptr(o_sc), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        outs = (o_rp, o_sp, o_ri, o_si, o_sc)
-        if out_device.type != "cuda":
-            outs = tuple(o.to(out_device) for o in outs)
-        return outs
+            _lib.call(dev, "gr_corr_gather", s, B, K1, K2, corr, rp, sp, ri, si, gs, int(gs is not None), o_rp, o_sp, o_ri,
+                      o_si, o_sc, ws=ws)
+        return _lib.like_input((o_rp, o_sp, o_ri, o_si, o_sc), out_device)
 
 
 class LocalGlobalRegistration(nn.Module):
@@ -198,10 +165,9 @@ class LocalGlobalRegistration(nn.Module):
         out_device = score_mat.device
         s, corr, n, pm_ws = self._pm._corr(score_mat, ref_knn_masks, src_knn_masks, True)
         dev = s.device
-        L = _lib.lib()
         B, K1, K2 = s.shape
-        rp, sp = _f32c(ref_knn_points, dev), _f32c(src_knn_points, dev)
-        gs = _f32c(global_scores, dev) if (self.use_global_score and global_scores is not None) else None
+        rp, sp = _lib.to_device(ref_knn_points, dev, **_F32), _lib.to_device(src_knn_points, dev, **_F32)
+        gs = _lib.to_device(global_scores, dev, **_F32) if (self.use_global_score and global_scores is not None) else None
         o_rp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_sp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_sc = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -209,27 +175,19 @@ class LocalGlobalRegistration(nn.Module):
         o_i = torch.empty((2, max(n, 1)), dtype=torch.int64, device=dev)
         transform = torch.eye(4, dtype=torch.float32, device=dev)
         if n > 0:
-            with torch.cuda.device(dev):
-                st = _lib.stream_ptr(dev)
-                _lib.check(L.gr_corr_gather(_lib.ptr(s), B, K1, K2, _lib.ptr(corr), _lib.ptr(rp), _lib.ptr(sp),
-                                            _lib.ptr(idx_dummy), _lib.ptr(idx_dummy), _lib.ptr(gs), int(gs is not None),
-                                            _lib.ptr(o_rp), _lib.ptr(o_sp), _lib.ptr(o_i[0]), _lib.ptr(o_i[1]),
-                                            _lib.ptr(o_sc), _lib.ptr(pm_ws), pm_ws.numel(), st))
-                ws2 = torch.empty(L.gr_lgr_workspace_bytes(B) + 256, dtype=torch.uint8, device=dev)
-                v_rp, v_sp, v_sc = o_rp, o_sp, o_sc
-                if self.correspondence_limit is not None and n > int(self.correspondence_limit):
-                    # verification set = top-`limit` global scores (local_global_registration.py:145-148)
-                    v_sc, sel = o_sc.topk(k=int(self.correspondence_limit), largest=True)
-                    v_rp, v_sp, v_sc = o_rp[sel].contiguous(), o_sp[sel].contiguous(), v_sc.contiguous()
-                _lib.check(L.gr_lgr_register_verify(_lib.ptr(o_rp), _lib.ptr(o_sp), _lib.ptr(o_sc), n, B, _lib.ptr(pm_ws),
-                                                    _lib.ptr(v_rp), _lib.ptr(v_sp), _lib.ptr(v_sc), v_sc.shape[0],
-                                                    float(self.acceptance_radius), int(self.correspondence_threshold),
-                                                    int(self.num_refinement_steps), _lib.ptr(transform), _lib.ptr(ws2),
-                                                    ws2.numel(), st))
-        outs = (o_rp, o_sp, o_sc, transform)
-        if out_device.type != "cuda":
-            outs = tuple(o.to(out_device) for o in outs)
-        return outs
+            _lib.call(dev, "gr_corr_gather", s, B, K1, K2, corr, rp, sp, idx_dummy, idx_dummy, gs, int(gs is not None), o_rp,
+                      o_sp, o_i[0], o_i[1], o_sc, ws=pm_ws)
+            # (a buffer of its own: pm_ws, the shared workspace, is an input of the registration)
+            ws2 = torch.empty(_lib.lib().gr_lgr_workspace_bytes(B) + 256, dtype=torch.uint8, device=dev)
+            v_rp, v_sp, v_sc = o_rp, o_sp, o_sc
+            if self.correspondence_limit is not None and n > int(self.correspondence_limit):
+                # verification set = top-`limit` global scores (local_global_registration.py:145-148)
+                v_sc, sel = o_sc.topk(k=int(self.correspondence_limit), largest=True)
+                v_rp, v_sp, v_sc = o_rp[sel].contiguous(), o_sp[sel].contiguous(), v_sc.contiguous()
+            _lib.call(dev, "gr_lgr_register_verify", o_rp, o_sp, o_sc, n, B, pm_ws, v_rp, v_sp, v_sc, v_sc.shape[0],
+                      float(self.acceptance_radius), int(self.correspondence_threshold), int(self.num_refinement_steps),
+                      transform, ws=ws2)
+        return _lib.like_input((o_rp, o_sp, o_sc, transform), out_device)
 
     @torch.no_grad()
     def forward_batch(self, ref_knn_points, src_knn_points, ref_knn_masks, src_knn_masks, score_mat, global_scores,
@@ -243,16 +201,13 @@ class LocalGlobalRegistration(nn.Module):
             raise NotImplementedError("forward_batch: correspondence_limit must be None")
         s, corr, n, pm_ws = self._pm._corr(score_mat, ref_knn_masks, src_knn_masks, True)
         dev = s.device
-        L = _lib.lib()
         P, K1, K2 = s.shape
-        poff = [0]
-        for c in patches_per_pair:
-            poff.append(poff[-1] + int(c))
+        poff = _lib.offsets(patches_per_pair)
         if poff[-1] != P:
             raise ValueError("patches_per_pair must sum to the number of patches")
         B = len(poff) - 1
-        rp, sp = _f32c(ref_knn_points, dev), _f32c(src_knn_points, dev)
-        gs = _f32c(global_scores, dev) if (self.use_global_score and global_scores is not None) else None
+        rp, sp = _lib.to_device(ref_knn_points, dev, **_F32), _lib.to_device(src_knn_points, dev, **_F32)
+        gs = _lib.to_device(global_scores, dev, **_F32) if (self.use_global_score and global_scores is not None) else None
         o_rp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_sp = torch.empty((n, 3), dtype=torch.float32, device=dev)
         o_sc = torch.empty((n,), dtype=torch.float32, device=dev)
@@ -262,16 +217,10 @@ class LocalGlobalRegistration(nn.Module):
             idx_dummy = torch.zeros((P, max(K1, K2)), dtype=torch.int64, device=dev)
             o_i = torch.empty((2, max(n, 1)), dtype=torch.int64, device=dev)
             d_poff = torch.tensor(poff, dtype=torch.int32).to(dev, non_blocking=False)
-            with torch.cuda.device(dev):
-                st = _lib.stream_ptr(dev)
-                if n > 0:
-                    _lib.check(L.gr_corr_gather(_lib.ptr(s), P, K1, K2, _lib.ptr(corr), _lib.ptr(rp), _lib.ptr(sp),
-                                                _lib.ptr(idx_dummy), _lib.ptr(idx_dummy), _lib.ptr(gs), int(gs is not None),
-                                                _lib.ptr(o_rp), _lib.ptr(o_sp), _lib.ptr(o_i[0]), _lib.ptr(o_i[1]),
-                                                _lib.ptr(o_sc), _lib.ptr(pm_ws), pm_ws.numel(), st))
-                ws2 = torch.empty(L.gr_lgr_workspace_bytes(P) + 256, dtype=torch.uint8, device=dev)
-                _lib.check(L.gr_lgr_register_seg(_lib.ptr(o_rp), _lib.ptr(o_sp), _lib.ptr(o_sc), n, P, _lib.ptr(pm_ws),
-                                                 _lib.ptr(d_poff), B, float(self.acceptance_radius),
-                                                 int(self.correspondence_threshold), int(self.num_refinement_steps),
-                                                 _lib.ptr(transforms), _lib.ptr(rows), _lib.ptr(ws2), ws2.numel(), st))
+            if n > 0:
+                _lib.call(dev, "gr_corr_gather", s, P, K1, K2, corr, rp, sp, idx_dummy, idx_dummy, gs, int(gs is not None),
+                          o_rp, o_sp, o_i[0], o_i[1], o_sc, ws=pm_ws)
+            ws2 = torch.empty(_lib.lib().gr_lgr_workspace_bytes(P) + 256, dtype=torch.uint8, device=dev)
+            _lib.call(dev, "gr_lgr_register_seg", o_rp, o_sp, o_sc, n, P, pm_ws, d_poff, B, float(self.acceptance_radius),
+                      int(self.correspondence_threshold), int(self.num_refinement_steps), transforms, rows, ws=ws2)
         return o_rp, o_sp, o_sc, transforms, rows

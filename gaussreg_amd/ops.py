@@ -34,18 +34,9 @@ def radius_search(q_points, s_points, q_lengths, s_lengths, radius, neighbor_lim
 
 # ---------------------------------------------------------------------------------------------
 # dense / partition operators (reference: modules/ops/pairwise_distance.py, pointcloud_partition.py)
-import ctypes  # noqa: E402
-
 import torch  # noqa: E402
 
 from . import _lib  # noqa: E402
-
-
-def _cuda_f32(t, name):
-    if t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be a float tensor")
-    dev = _lib.require_gpu()
-    return (t if t.is_cuda else t.to(dev)).contiguous()
 
 
 def pairwise_distance(x, y, normalized=False, channel_first=False):
@@ -56,18 +47,14 @@ def pairwise_distance(x, y, normalized=False, channel_first=False):
     lead = x.shape[:-2]
     if y.shape[:-2] != lead:
         raise RuntimeError("pairwise_distance: x and y must have the same leading (batch) dimensions")
-    xs = _cuda_f32(x, "x").reshape(-1, x.shape[-2], x.shape[-1])
-    ys = _cuda_f32(y, "y").reshape(-1, y.shape[-2], y.shape[-1])
-    L = _lib.lib()
+    xs = _lib.to_device(x, None, torch.float32, "x", cast=False).reshape(-1, x.shape[-2], x.shape[-1])
+    ys = _lib.to_device(y, None, torch.float32, "y", cast=False).reshape(-1, y.shape[-2], y.shape[-1])
     B, N, C = xs.shape
     M = ys.shape[1]
     out = torch.empty((B, N, M), dtype=torch.float32, device=xs.device)
-    with torch.cuda.device(xs.device):
-        ws = _lib.workspace(xs.device, L.gr_pairwise_distance_batch_workspace_bytes(B, N, M))
-        _lib.check(L.gr_pairwise_distance_batch(_lib.ptr(xs), _lib.ptr(ys), B, N, M, C, int(bool(normalized)), _lib.ptr(out),
-                                                _lib.ptr(ws), ws.numel(), _lib.stream_ptr(xs.device)))
-    out = out.reshape(*lead, N, M)
-    return out if out_device.type == "cuda" else out.to(out_device)
+    _lib.call(xs.device, "gr_pairwise_distance_batch", xs, ys, B, N, M, C, int(bool(normalized)), out,
+              ws=_lib.lib().gr_pairwise_distance_batch_workspace_bytes(B, N, M))
+    return _lib.like_input(out.reshape(*lead, N, M), out_device)
 
 
 @torch.no_grad()
@@ -75,26 +62,20 @@ def point_to_node_partition(points, nodes, point_limit, return_count=False):
     """pointcloud_partition.py:61-111 without the (M, N) matrix.  Returns
     (point_to_node (N,), [node_sizes (M,)], node_masks (M,), node_knn_indices (M,K), node_knn_masks (M,K))."""
     out_device = points.device
-    p = _cuda_f32(points, "points")
-    nd = _cuda_f32(nodes, "nodes")
-    L = _lib.lib()
+    p = _lib.to_device(points, None, torch.float32, "points", cast=False)
+    nd = _lib.to_device(nodes, None, torch.float32, "nodes", cast=False)
     N, M, K = p.shape[0], nd.shape[0], int(point_limit)
     dev = p.device
     p2n = torch.empty((N,), dtype=torch.int64, device=dev)
     masks = torch.empty((M,), dtype=torch.bool, device=dev)
     knn_idx = torch.empty((M, K), dtype=torch.int64, device=dev)
     knn_masks = torch.empty((M, K), dtype=torch.bool, device=dev)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_point_to_node_workspace_bytes(N, M))
-        _lib.check(L.gr_point_to_node_partition(_lib.ptr(p), N, _lib.ptr(nd), M, K, _lib.ptr(p2n), _lib.ptr(masks),
-                                                _lib.ptr(knn_idx), _lib.ptr(knn_masks), _lib.ptr(ws), ws.numel(),
-                                                _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_point_to_node_partition", p, N, nd, M, K, p2n, masks, knn_idx, knn_masks,
+              ws=_lib.lib().gr_point_to_node_workspace_bytes(N, M))
     res = [p2n, masks, knn_idx, knn_masks]
     if return_count:
         res.insert(1, torch.bincount(p2n, minlength=M))
-    if out_device.type != "cuda":
-        res = [r.to(out_device) for r in res]
-    return tuple(res)
+    return _lib.like_input(tuple(res), out_device)
 
 
 @torch.no_grad()
@@ -103,16 +84,11 @@ def point_to_node_partition_batch(points, point_lengths, nodes, node_lengths, po
     (gr_point_to_node_partition_batch): `points` (sum N_c, 3) / `nodes` (sum M_c, 3) with per-cloud lengths.  Returns
     (point_to_node (sum N,), node_masks (sum M,), node_knn_indices (sum M, K), node_knn_masks (sum M, K)); indices are LOCAL
     to their cloud, exactly what the single-cloud call returns for it."""
-    p = _cuda_f32(points, "points")
-    nd = _cuda_f32(nodes, "nodes")
-    L = _lib.lib()
+    p = _lib.to_device(points, None, torch.float32, "points", cast=False)
+    nd = _lib.to_device(nodes, None, torch.float32, "nodes", cast=False)
     K = int(point_limit)
     dev = p.device
-    po, no = [0], [0]
-    for n in point_lengths:
-        po.append(po[-1] + int(n))
-    for m in node_lengths:
-        no.append(no[-1] + int(m))
+    po, no = _lib.offsets(point_lengths), _lib.offsets(node_lengths)
     if len(po) != len(no) or po[-1] != p.shape[0] or no[-1] != nd.shape[0]:
         raise ValueError("lengths do not match the stacked tensors")
     nclouds = len(po) - 1
@@ -121,11 +97,8 @@ def point_to_node_partition_batch(points, point_lengths, nodes, node_lengths, po
     knn_idx = torch.empty((no[-1], K), dtype=torch.int64, device=dev)
     knn_masks = torch.empty((no[-1], K), dtype=torch.bool, device=dev)
     h_po, h_no = _lib.host_i64(po), _lib.host_i64(no)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_point_to_node_batch_workspace_bytes(h_po, h_no, nclouds))
-        _lib.check(L.gr_point_to_node_partition_batch(_lib.ptr(p), h_po, _lib.ptr(nd), h_no, nclouds, K, _lib.ptr(p2n),
-                                                      _lib.ptr(masks), _lib.ptr(knn_idx), _lib.ptr(knn_masks), _lib.ptr(ws),
-                                                      ws.numel(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_point_to_node_partition_batch", p, h_po, nd, h_no, nclouds, K, p2n, masks, knn_idx, knn_masks,
+              ws=_lib.lib().gr_point_to_node_batch_workspace_bytes(h_po, h_no, nclouds))
     return p2n, masks, knn_idx, knn_masks
 
 
@@ -167,22 +140,16 @@ def index_select(data, index, dim):
             flag = torch.zeros(1, dtype=torch.int32, device=dev)
             _gather_flags[key] = flag
         if m > 0 and c > 0:
-            L = _lib.lib()
             eager = m <= 65536
             if eager:
                 # a small gather is checked eagerly like torch's: its own flag word, so an earlier LARGE gather's pending
                 # error is neither raised here nor lost (that one poisons its rows with NaN and is reported by
                 # gather_error_pending)
                 own = torch.zeros(1, dtype=torch.int32, device=dev)
-            with torch.cuda.device(dev):
-                _lib.check(L.gr_gather_rows(_lib.ptr(flat), n, max(c, 1), _lib.ptr(idx), m, _lib.ptr(res),
-                                            _lib.ptr(own if eager else flag), _lib.stream_ptr(dev)))
+            _lib.call(dev, "gr_gather_rows", flat, n, max(c, 1), idx, m, res, own if eager else flag)
             if eager and int(own.item()) != 0:
                 raise IndexError("index out of range in index_select")
-        out = res.reshape((m,) + tuple(rest)).movedim(0, dim)
-        if out_device.type != "cuda":
-            out = out.to(out_device)
-        out = out.contiguous()
+        out = _lib.like_input(res.reshape((m,) + tuple(rest)).movedim(0, dim), out_device).contiguous()
     if index.dim() > 1:
         out = out.view(*(tuple(data.shape[:dim]) + tuple(index.shape) + tuple(data.shape[dim:][1:])))
     return out

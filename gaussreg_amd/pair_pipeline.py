@@ -109,7 +109,6 @@ class PositionDescriptor:
         """x (..., 3) -> (..., C).  transforms (k, 3, 4) / transform_id (...,) int32 (-1: identity): the row's pose;
         mask (...,) bool: rows to zero."""
         from . import _lib
-        L = _lib.lib()
         lead = x.shape[:-1]
         p = x.reshape(-1, 3).to(torch.float32).contiguous()
         n, C = p.shape[0], self.W.shape[1]
@@ -117,10 +116,8 @@ class PositionDescriptor:
         T = None if transforms is None else transforms.reshape(-1, 12).to(torch.float32).contiguous()
         tid = None if transform_id is None else transform_id.reshape(-1).to(torch.int32).contiguous()
         m = None if mask is None else mask.reshape(-1).to(torch.bool).contiguous()
-        with torch.cuda.device(p.device):
-            _lib.check(L.gr_standin_descriptors(_lib.ptr(p), n, _lib.ptr(T), _lib.ptr(tid), _lib.ptr(m), _lib.ptr(self.W),
-                                                _lib.ptr(self.b), C, float(self.scale), int(bool(normalize)), _lib.ptr(out),
-                                                _lib.stream_ptr(p.device)))
+        _lib.call(p.device, "gr_standin_descriptors", p, n, T, tid, m, self.W, self.b, C, float(self.scale), int(bool(normalize)),
+                  out)
         return out.reshape(*lead, C)
 
 

@@ -52,10 +52,7 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
-FAST_EXP = 1  # GR_RASTER_FAST_EXP (include/gaussreg_hip.h)
-SPLIT = 2     # GR_RASTER_SPLIT
-SHARE = 4     # GR_RASTER_SHARE
-BWD_COLOR_ONLY = 8  # GR_RASTER_BWD_COLOR_ONLY
+FAST_EXP, SPLIT, SHARE, BWD_COLOR_ONLY = (_lib.DEFINES["GR_RASTER_" + f] for f in ("FAST_EXP", "SPLIT", "SHARE", "BWD_COLOR_ONLY"))
 _ENV_FAST = None
 _bin_hint = {}  # (device, P, V, W, H) -> (bytes of the binning buffer, largest chunk) the last call of that shape needed
 
@@ -582,15 +579,12 @@ class GaussianRasterizer(torch.nn.Module):
     def markVisible(self, positions):
         with torch.no_grad():
             dev = _lib.require_gpu()
-            L = _lib.lib()
             p = positions.detach().to(device=positions.device if positions.is_cuda else dev,
                                       dtype=torch.float32).contiguous()
             present = torch.zeros((p.shape[0],), dtype=torch.uint8, device=p.device)
             vm = (ctypes.c_float * 16)(*self.raster_settings.viewmatrix.detach().to("cpu", torch.float32)
                                        .reshape(-1).tolist())
-            with torch.cuda.device(p.device):
-                _lib.check(L.gr_raster_mark_visible(p.shape[0], _lib.ptr(p), vm, _lib.ptr(present),
-                                                    _lib.stream_ptr(p.device)))
+            _lib.call(p.device, "gr_raster_mark_visible", p.shape[0], p, vm, present)
             return present.bool()
 
     def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,

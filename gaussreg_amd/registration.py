@@ -13,10 +13,8 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
     """Same positional signature as the reference wrapper (open3d.py:169-176); returns a (4,4) float32 tensor
     (the reference returns a float64 numpy array).  `correspondences` (C,2) selects rows of src / ref."""
     dev = _lib.require_gpu()
-    L = _lib.lib()
-    s = torch.as_tensor(src_points, dtype=torch.float32)
+    s = _lib.to_device(torch.as_tensor(src_points, dtype=torch.float32), dev)
     r = torch.as_tensor(ref_points, dtype=torch.float32)
-    s = (s if s.is_cuda else s.to(dev)).contiguous()
     dev = s.device
     r = r.to(dev).contiguous()
     if correspondences is not None:
@@ -25,12 +23,9 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
     n = s.shape[0]
     out = torch.empty((4, 4), dtype=torch.float32, device=dev)
     stats = torch.zeros(2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_ransac_workspace_bytes(int(num_iterations)))
-        _lib.check(L.gr_ransac_similarity(_lib.ptr(s), _lib.ptr(r), n, int(ransac_n), int(num_iterations), int(seed),
-                                          float(distance_threshold), int(bool(with_scaling)), int(bool(refine)),
-                                          _lib.ptr(out), _lib.ptr(stats), _lib.ptr(ws), ws.numel(),
-                                          _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_ransac_similarity", s, r, n, int(ransac_n), int(num_iterations), int(seed), float(distance_threshold),
+              int(bool(with_scaling)), int(bool(refine)), out, stats,
+              ws=_lib.lib().gr_ransac_workspace_bytes(int(num_iterations)))
     return (out, stats) if return_stats else out
 
 
@@ -43,7 +38,6 @@ def registration_with_ransac_batch(src_points, ref_points, row_offsets, fallback
     tensor on the device, B + 1 entries) and uses seed + b.  A pair with fewer than ransac_n rows keeps
     fallback_transforms[b] (model.py:209-220; default identity).  Returns (B,4,4) float32 on the device, no host
     synchronisation."""
-    L = _lib.lib()
     s = src_points.contiguous()
     r = ref_points.contiguous()
     dev = s.device
@@ -53,12 +47,9 @@ def registration_with_ransac_batch(src_points, ref_points, row_offsets, fallback
     stats = torch.zeros((B, 2), dtype=torch.int32, device=dev)
     fb = None if fallback_transforms is None else fallback_transforms.to(device=dev, dtype=torch.float32).contiguous()
     if B > 0:
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_ransac_seg_workspace_bytes(int(num_iterations), B))
-            _lib.check(L.gr_ransac_similarity_seg(_lib.ptr(s), _lib.ptr(r), _lib.ptr(off), B, int(ransac_n),
-                                                  int(num_iterations), int(seed), float(distance_threshold),
-                                                  int(bool(with_scaling)), int(bool(refine)), _lib.ptr(fb), _lib.ptr(out),
-                                                  _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_ransac_similarity_seg", s, r, off, B, int(ransac_n), int(num_iterations), int(seed),
+                  float(distance_threshold), int(bool(with_scaling)), int(bool(refine)), fb, out, stats,
+                  ws=_lib.lib().gr_ransac_seg_workspace_bytes(int(num_iterations), B))
     return (out, stats) if return_stats else out
 
 
@@ -70,18 +61,14 @@ def farthest_point_sampling(points, lengths, num_samples, start_indices=None, ga
     `gather=True`: returns the sampled POINTS instead, a list of (k_b, 3) views of one stacked tensor (one row gather for
     the whole call instead of one indexing launch per cloud)."""
     dev = _lib.require_gpu()
-    L = _lib.lib()
-    p = torch.as_tensor(points, dtype=torch.float32)
-    p = (p if p.is_cuda else p.to(dev)).contiguous()
+    p = _lib.to_device(torch.as_tensor(points, dtype=torch.float32), dev)
     dev = p.device
     lens = [int(x) for x in (lengths.tolist() if hasattr(lengths, "tolist") else lengths)]
     ks = [int(x) for x in (num_samples.tolist() if hasattr(num_samples, "tolist") else num_samples)]
     st = None if start_indices is None else _lib.host_i64([int(x) for x in start_indices])
     out = torch.empty((sum(ks),), dtype=torch.int64, device=dev)
-    with torch.cuda.device(dev):
-        ws = _lib.workspace(dev, L.gr_fps_workspace_bytes(p.shape[0], len(lens)))
-        _lib.check(L.gr_fps(_lib.ptr(p), _lib.host_i64(lens), _lib.host_i64(ks), st, p.shape[0], len(lens), _lib.ptr(out),
-                            _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_fps", p, _lib.host_i64(lens), _lib.host_i64(ks), st, p.shape[0], len(lens), out,
+              ws=_lib.lib().gr_fps_workspace_bytes(p.shape[0], len(lens)))
     if gather:
         from .ops import index_select
         base = torch.tensor([0] + lens[:-1], dtype=torch.int64).cumsum(0).to(dev)        # first row of every cloud in the stack

@@ -25,15 +25,11 @@ from .kpconv import differentiable_active
 
 def _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H):
     """gr_rpe_attention on the float32 contiguous tensors of one batch element -> hidden (N,C), scores (H,N,M)."""
-    L = _lib.lib()
     dev = q2.device
     (N, C), M = q2.shape, k2.shape[0]
     scores = torch.empty((H, N, M), dtype=torch.float32, device=dev)
     hidden = torch.empty((N, C), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L.gr_rpe_attention(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2), _lib.ptr(k2), _lib.ptr(v2),
-                                      _lib.ptr(fac), _lib.ptr(kw), _lib.ptr(km), N, M, C, H, _lib.ptr(scores),
-                                      _lib.ptr(hidden), _lib.stream_ptr(dev)))
+    _lib.call(dev, "gr_rpe_attention", emb, u, add, q2, k2, v2, fac, kw, km, N, M, C, H, scores, hidden)
     return hidden, scores
 
 
@@ -54,7 +50,6 @@ class _RPEAttentionFunction(torch.autograd.Function):
         emb, u, q2, k2, v2, scores, fac, kw = ctx.saved_tensors
         if grad_hidden is None and grad_scores is None:
             return (None,) * 10
-        L = _lib.lib()
         dev = q2.device
         (N, C), M, H = q2.shape, k2.shape[0], ctx.H
         gh = torch.zeros_like(q2) if grad_hidden is None else grad_hidden.to(torch.float32).contiguous()
@@ -62,13 +57,8 @@ class _RPEAttentionFunction(torch.autograd.Function):
         gq, gk, gv, gu = torch.empty_like(q2), torch.empty_like(k2), torch.empty_like(v2), torch.empty_like(u)
         gadd = torch.empty((N, H), dtype=torch.float32, device=dev)
         gemb = torch.empty_like(emb) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_rpe_attention_backward_workspace_bytes(N, M, H))
-            _lib.check(L.gr_rpe_attention_backward(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(q2), _lib.ptr(k2), _lib.ptr(v2),
-                                                   _lib.ptr(scores), _lib.ptr(fac), _lib.ptr(kw), _lib.ptr(gh), _lib.ptr(gs),
-                                                   N, M, C, H, _lib.ptr(gq), _lib.ptr(gk), _lib.ptr(gv), _lib.ptr(gu),
-                                                   _lib.ptr(gadd), _lib.ptr(gemb), _lib.ptr(ws), ws.numel(),
-                                                   _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_rpe_attention_backward", emb, u, q2, k2, v2, scores, fac, kw, gh, gs, N, M, C, H, gq, gk, gv, gu,
+                  gadd, gemb, ws=_lib.lib().gr_rpe_attention_backward_workspace_bytes(N, M, H))
         return gemb, gu, gadd, gq, gk, gv, None, None, None, None
 
 
@@ -106,8 +96,7 @@ class RPEMultiHeadAttention(nn.Module):
     def _forward_inference(self, input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors, lengths):
         if lengths is not None:
             return self._forward_ragged(input_q, input_k, input_v, embed_qk, lengths)
-        dev = _lib.require_gpu()
-        L = _lib.lib()
+        _lib.require_gpu()
         if not input_q.is_cuda:
             raise RuntimeError("RPEMultiHeadAttention: inputs must live on the GPU")
         dev = input_q.device
@@ -120,14 +109,10 @@ class RPEMultiHeadAttention(nn.Module):
         fac = None if attention_factors is None else attention_factors.to(torch.float32).contiguous()
         kw = None if key_weights is None else key_weights.to(torch.float32).contiguous()
         km = None if key_masks is None else key_masks.to(torch.uint8).contiguous()
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            for b in range(B):
-                q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
-                _lib.check(L.gr_rpe_attention(_lib.ptr(emb[b]), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2),
-                                              _lib.ptr(k2), _lib.ptr(v2), _lib.ptr(None if fac is None else fac[b]),
-                                              _lib.ptr(None if kw is None else kw[b]), _lib.ptr(None if km is None else km[b]),
-                                              N, M, C, H, _lib.ptr(scores[b]), _lib.ptr(hidden[b]), st))
+        for b in range(B):
+            q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
+            _lib.call(dev, "gr_rpe_attention", emb[b], u, add, q2, k2, v2, None if fac is None else fac[b],
+                      None if kw is None else kw[b], None if km is None else km[b], N, M, C, H, scores[b], hidden[b])
         if not isinstance(self.dropout, nn.Identity):
             scores = self.dropout(scores)  # inference: identity (the reference applies dropout to the scores before @ v)
         return hidden, scores
@@ -205,7 +190,6 @@ class RPEMultiHeadAttention(nn.Module):
                                "inside differentiable())" % (m, heads, max_keys))
 
     def _forward_ragged(self, input_q, input_k, input_v, embed_list, lengths):
-        L = _lib.lib()
         dev = input_q.device
         B, N, C = input_q.shape
         H, ch = self.num_heads, self.d_model_per_head
@@ -214,17 +198,13 @@ class RPEMultiHeadAttention(nn.Module):
         hidden = torch.zeros((B, N, C), dtype=torch.float32, device=dev)
         nmax = max(int(n) for n in lengths)
         scores = torch.empty((H, nmax, nmax), dtype=torch.float32, device=dev)   # scratch: the kernel writes it, nobody reads
-        with torch.cuda.device(dev):
-            st = _lib.stream_ptr(dev)
-            for b in range(B):
-                n = int(lengths[b])
-                emb = embed_list[b]
-                if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
-                    raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
-                if n == 0:
-                    continue
-                q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
-                _lib.check(L.gr_rpe_attention(_lib.ptr(emb), _lib.ptr(u), _lib.ptr(add), _lib.ptr(q2), _lib.ptr(k2),
-                                              _lib.ptr(v2), None, None, None, n, n, C, H, _lib.ptr(scores),
-                                              _lib.ptr(hidden[b]), st))
+        for b in range(B):
+            n = int(lengths[b])
+            emb = embed_list[b]
+            if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
+                raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
+            if n == 0:
+                continue
+            q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
+            _lib.call(dev, "gr_rpe_attention", emb, u, add, q2, k2, v2, None, None, None, n, n, C, H, scores, hidden[b])
         return hidden, None

@@ -87,41 +87,35 @@ def densify_and_prune(opt, stats, max_grad, min_opacity, extent, max_screen_size
         if noise.dtype != torch.float32 or noise.device != dev or not noise.is_contiguous():
             raise ValueError(f"noise: must be a contiguous float32 tensor on {dev}")
     _check_state(opt, P, dev)
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        stream = _lib.stream_ptr(dev)
-        source = torch.empty(2 * P, dtype=torch.int32, device=dev)
-        kind = torch.empty(2 * P, dtype=torch.uint8, device=dev)
-        counts_dev = torch.empty(4, dtype=torch.int32, device=dev)
-        h_counts = _lib.host_i64([0] * 4)
-        nbytes = L.gr_gs_densify_plan_workspace_bytes(P)
-        ws = _lib.workspace(dev, nbytes) if nbytes else None
-        _lib.check(L.gr_gs_densify_plan(_lib.ptr(roles["scaling"]), _lib.ptr(roles["opacity"]), _lib.ptr(stats.grad_accum),
-                                        _lib.ptr(stats.denom), _lib.ptr(stats.max_radii), P, float(max_grad), float(min_opacity),
-                                        float(extent), float(percent_dense), int(max_screen_size is not None),
-                                        float(max_screen_size or 0.0), _lib.ptr(source), _lib.ptr(kind), _lib.ptr(counts_dev),
-                                        h_counts, _lib.ptr(ws), nbytes, stream))
-        counts = tuple(int(c) for c in h_counts[:4])
-        P_new = sum(counts)
-        # new tensors and the group table; nothing of opt or stats is replaced before every launch has been accepted
-        entries, rebuilt = [], []
-        for group in opt.param_groups:
-            old = group["params"][0]
-            st = opt.state.get(old)
-            new = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
-            new_m = torch.empty_like(new) if st else None
-            new_v = torch.empty_like(new) if st else None
-            name = group.get("name")
-            role = {"xyz": _lib.GS_DENSIFY_XYZ, "scaling": _lib.GS_DENSIFY_SCALING}.get(name, _lib.GS_DENSIFY_CARRIED)
-            entries.append(_lib.GsDensifyGroup(_lib.ptr(old), _lib.ptr(new), _lib.ptr(st["exp_avg"] if st else None),
-                                               _lib.ptr(new_m), _lib.ptr(st["exp_avg_sq"] if st else None), _lib.ptr(new_v),
-                                               old.numel() // P if P else 0, role))
-            rebuilt.append((group, old, st, new, new_m, new_v))
-        for i in range(0, len(entries), _lib.GS_ADAM_MAX_GROUPS):
-            chunk = entries[i:i + _lib.GS_ADAM_MAX_GROUPS]
-            table = (_lib.GsDensifyGroup * len(chunk))(*chunk)
-            _lib.check(L.gr_gs_densify_apply(table, len(chunk), P, P_new, _lib.ptr(source), _lib.ptr(kind),
-                                             _lib.ptr(roles["scaling"]), _lib.ptr(roles["rotation"]), _lib.ptr(noise), stream))
+    source = torch.empty(2 * P, dtype=torch.int32, device=dev)
+    kind = torch.empty(2 * P, dtype=torch.uint8, device=dev)
+    counts_dev = torch.empty(4, dtype=torch.int32, device=dev)
+    h_counts = _lib.host_i64([0] * 4)
+    _lib.call(dev, "gr_gs_densify_plan", roles["scaling"], roles["opacity"], stats.grad_accum, stats.denom, stats.max_radii, P,
+              float(max_grad), float(min_opacity), float(extent), float(percent_dense), int(max_screen_size is not None),
+              float(max_screen_size or 0.0), source, kind, counts_dev, h_counts,
+              ws=_lib.lib().gr_gs_densify_plan_workspace_bytes(P))
+    counts = tuple(int(c) for c in h_counts[:4])
+    P_new = sum(counts)
+    # new tensors and the group table; nothing of opt or stats is replaced before every launch has been accepted
+    entries, rebuilt = [], []
+    for group in opt.param_groups:
+        old = group["params"][0]
+        st = opt.state.get(old)
+        new = torch.empty((P_new,) + tuple(old.shape[1:]), dtype=torch.float32, device=dev)
+        new_m = torch.empty_like(new) if st else None
+        new_v = torch.empty_like(new) if st else None
+        name = group.get("name")
+        role = {"xyz": _lib.GS_DENSIFY_XYZ, "scaling": _lib.GS_DENSIFY_SCALING}.get(name, _lib.GS_DENSIFY_CARRIED)
+        fields = (old, new, st["exp_avg"] if st else None, new_m, st["exp_avg_sq"] if st else None, new_v)
+        entries.append(_lib.GsDensifyGroup(*(_lib.device_ptr(t, dev, f"gr_gs_densify_apply: param group {name}") for t in fields),
+                                           old.numel() // P if P else 0, role))
+        rebuilt.append((group, old, st, new, new_m, new_v))
+    for i in range(0, len(entries), _lib.GS_ADAM_MAX_GROUPS):
+        chunk = entries[i:i + _lib.GS_ADAM_MAX_GROUPS]
+        table = (_lib.GsDensifyGroup * len(chunk))(*chunk)
+        _lib.call(dev, "gr_gs_densify_apply", table, len(chunk), P, P_new, source, kind, roles["scaling"], roles["rotation"],
+                  noise)
     tensors = {}
     for gi, (group, old, st, new, new_m, new_v) in enumerate(rebuilt):
         if isinstance(old, torch.nn.Parameter):

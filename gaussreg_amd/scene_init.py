@@ -40,20 +40,15 @@ def _run(points, k, want_dist2, want_index, want_mean):
     _check_points(points, k)
     points = points.detach()
     dev, N = points.device, points.shape[0]
-    L = _lib.lib()
-    with torch.cuda.device(dev):
-        dist2 = torch.empty((N, k), dtype=torch.float32, device=dev) if want_dist2 else None
-        index = torch.empty((N, k), dtype=torch.int64, device=dev) if want_index else None
-        mean = torch.empty(N, dtype=torch.float32, device=dev) if want_mean else None
-        nbytes = L.gr_gs_knn_workspace_bytes(N, k)
-        ws = _lib.workspace(dev, nbytes)
-        rc = L.gr_gs_knn(_lib.ptr(points), N, k, _lib.ptr(dist2), _lib.ptr(index), _lib.ptr(mean), _lib.ptr(ws), nbytes,
-                         _lib.stream_ptr(dev))
-    if rc != 0:
-        msg = (L.gr_last_error() or b"").decode()
-        if "points must be finite" in msg:
-            raise ValueError("points must be finite")
-        _lib.check(rc)
+    dist2 = torch.empty((N, k), dtype=torch.float32, device=dev) if want_dist2 else None
+    index = torch.empty((N, k), dtype=torch.int64, device=dev) if want_index else None
+    mean = torch.empty(N, dtype=torch.float32, device=dev) if want_mean else None
+    try:
+        _lib.call(dev, "gr_gs_knn", points, N, k, dist2, index, mean, ws=_lib.lib().gr_gs_knn_workspace_bytes(N, k))
+    except RuntimeError as e:
+        if "points must be finite" in str(e):
+            raise ValueError("points must be finite") from None
+        raise
     return dist2, index, mean
 
 

@@ -128,26 +128,23 @@ class GaussianAdam(torch.optim.Optimizer):
             t = int(st["step"].item() if isinstance(st["step"], torch.Tensor) else st["step"]) + 1
             beta1, beta2 = group["betas"]
             K = p.numel() // P if P else 0
-            entry = _lib.GsAdamGroup(_lib.ptr(p), _lib.ptr(p.grad), _lib.ptr(st["exp_avg"]), _lib.ptr(st["exp_avg_sq"]),
+            what = f"gr_gs_adam_step: param group {group.get('name', gi)}"
+            entry = _lib.GsAdamGroup(*(_lib.device_ptr(t, dev, what) for t in (p, p.grad, st["exp_avg"], st["exp_avg_sq"])),
                                      float(group["lr"]), K)
             launches.setdefault((t, float(beta1), float(beta2), float(group["eps"])), []).append((entry, st))
         if not launches:
             return loss
-        L = _lib.lib()
-        with torch.cuda.device(dev):
-            stream = _lib.stream_ptr(dev)
-            for (t, beta1, beta2, eps), entries in launches.items():
-                bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
-                for i in range(0, len(entries), _lib.GS_ADAM_MAX_GROUPS):
-                    chunk = entries[i:i + _lib.GS_ADAM_MAX_GROUPS]
-                    table = (_lib.GsAdamGroup * len(chunk))(*[e for e, _ in chunk])
-                    _lib.check(L.gr_gs_adam_step(table, len(chunk), P, beta1, beta2, eps, bc1, bc2, _lib.ptr(mask),
-                                                 _lib.ptr(radii), V, stream))
-                for _, st in entries:
-                    if isinstance(st["step"], torch.Tensor):
-                        st["step"] += 1
-                    else:
-                        st["step"] = torch.tensor(float(t), dtype=torch.float32)
+        for (t, beta1, beta2, eps), entries in launches.items():
+            bc1, bc2 = 1.0 - beta1 ** t, 1.0 - beta2 ** t
+            for i in range(0, len(entries), _lib.GS_ADAM_MAX_GROUPS):
+                chunk = entries[i:i + _lib.GS_ADAM_MAX_GROUPS]
+                table = (_lib.GsAdamGroup * len(chunk))(*[e for e, _ in chunk])
+                _lib.call(dev, "gr_gs_adam_step", table, len(chunk), P, beta1, beta2, eps, bc1, bc2, mask, radii, V)
+            for _, st in entries:
+                if isinstance(st["step"], torch.Tensor):
+                    st["step"] += 1
+                else:
+                    st["step"] = torch.tensor(float(t), dtype=torch.float32)
         return loss
 
     @torch.no_grad()
@@ -201,9 +198,7 @@ class DensifyStats:
             raise ValueError(f"means2D_grad and radii must be on {dev}")
         if not (g.is_contiguous() and r.is_contiguous()):
             raise ValueError("means2D_grad and radii must be contiguous")
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().gr_gs_densify_stats(_lib.ptr(g), _lib.ptr(r), P, int(g.shape[0]), _lib.ptr(self.grad_accum),
-                                                      _lib.ptr(self.denom), _lib.ptr(self.max_radii), _lib.stream_ptr(dev)))
+        _lib.call(dev, "gr_gs_densify_stats", g, r, P, int(g.shape[0]), self.grad_accum, self.denom, self.max_radii)
 
     def mean_grad(self):
         """grad_accum / max(denom, 1): upstream's average screen-space gradient norm per Gaussian."""

@@ -20,9 +20,8 @@ class LearnableLogOptimalTransport(nn.Module):
         row and column -- what model.py:197-198 slices off right after the call; `out`: a preallocated contiguous float32
         CUDA tensor of that shape to write into."""
         dev = _lib.require_gpu()
-        L = _lib.lib()
         out_device = scores.device
-        s = (scores if scores.is_cuda else scores.to(dev)).to(torch.float32).contiguous()
+        s = _lib.to_device(scores, dev, torch.float32)
         dev = s.device
         B, M, N = s.shape
         rm = None if row_masks is None else row_masks.to(device=dev, dtype=torch.bool).contiguous()
@@ -33,13 +32,9 @@ class LearnableLogOptimalTransport(nn.Module):
             out = torch.empty(shape, dtype=torch.float32, device=dev)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
             raise ValueError("out must be a contiguous float32 tensor of shape %s on %s" % (shape, dev))
-        with torch.cuda.device(dev):
-            ws = _lib.workspace(dev, L.gr_sinkhorn_workspace_bytes(B))
-            _lib.check(L.gr_sinkhorn(_lib.ptr(s), B, M, N, _lib.ptr(rm), _lib.ptr(cm), _lib.ptr(alpha),
-                                     int(self.num_iterations), float(self.inf), int(bool(drop_dustbin)), _lib.ptr(out),
-                                     _lib.ptr(ws), ws.numel(),
-                                     _lib.stream_ptr(dev)))
-        return out if out_device.type == "cuda" else out.to(out_device)
+        _lib.call(dev, "gr_sinkhorn", s, B, M, N, rm, cm, alpha, int(self.num_iterations), float(self.inf),
+                  int(bool(drop_dustbin)), out, ws=_lib.lib().gr_sinkhorn_workspace_bytes(B))
+        return _lib.like_input(out, out_device)
 
     def __repr__(self):
         return self.__class__.__name__ + '(num_iterations={})'.format(self.num_iterations)
