@@ -90,7 +90,7 @@ __global__ __launch_bounds__(PM_T) void corr_matrix_kernel(
 
 // The same for k <= 4 (GaussReg: k = 3) in ONE scan per row and per column: the k largest entries of a line, ties to the
 // lowest index, are what k rounds of "largest not yet taken" (strict >) pick.  A thread keeps them in registers as a sorted
-// list and bubbles every element down it (strict >, so an equal later element never displaces an earlier one); threads
+// list and inserts every element into it (strict >, so an equal later element never displaces an earlier one); threads
 // 0..127 take the rows while threads 128..255 take the columns; the selections are k indices per line instead of a flag byte
 // per entry, so the matrix alone is in LDS and two workgroups share a CU.  (The k-round kernel above spent 3 x 128 dependent
 // LDS round trips per line, rows and columns one after the other, on half of its threads: 4.3 ms per 16 384 patches.)
@@ -115,16 +115,20 @@ __device__ __forceinline__ void pm_topk_line(const float* __restrict__ base, int
     for (int u = 0; u < 4; ++u) {
       float cv = v[u];
       int ci = (t0 + u < len && cv > thr) ? t0 + u : -1;
+      bool shift = false;
 #pragma unroll
       for (int s = 0; s < PM_KMAX; ++s) {
-        // the carried element takes slot s if the slot is empty or holds a strictly smaller value; what it displaces moves on
-        const bool take = s < k && ci >= 0 && (ti[s] < 0 || cv > tv[s]);
+        // the new element takes slot s if the slot is empty or holds a strictly smaller value; from there on every slot hands
+        // its element to the next one.  (A displaced element is ahead of everything below it, equal values included: comparing
+        // it again with > dropped it in favour of an equal value of HIGHER index.)
+        const bool take = s < k && ci >= 0 && (shift || ti[s] < 0 || cv > tv[s]);
         const float ov = tv[s];
         const int oi = ti[s];
         tv[s] = take ? cv : ov;
         ti[s] = take ? ci : oi;
         cv = take ? ov : cv;
         ci = take ? oi : ci;
+        shift = shift || take;
       }
     }
   }

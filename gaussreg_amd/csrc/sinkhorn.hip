@@ -16,6 +16,7 @@ constexpr int SK_PARTS = 4;   // lanes per row / column (adjacent lanes: their p
 constexpr int SK_T = 512;     // 8 waves, two per SIMD: 128 rows (columns) x 4 lanes; the demo shape's 129th row and column
                               // (the dustbins) are reduced by whole waves on the side
 constexpr int SK_MAIN = SK_T / SK_PARTS;  // rows / columns that get their own four lanes
+constexpr int SK_SIDE = SK_T / WAVE / 2;  // scaling form: rows (even waves) / columns (odd waves) beyond SK_MAIN, one per wave
 constexpr int SK_MAXD = 144;  // largest M + 1 / N + 1 supported
 constexpr int SK_PER = SK_MAXD / SK_PARTS;  // elements of a row / column one lane reduces (<= 36)
 
@@ -155,13 +156,16 @@ __device__ __forceinline__ void sinkhorn_matrix(const int b, const float* __rest
   // vectors (any constant is exact; these keep the exponents near zero without a third barrier).  Masked rows / columns
   // (scores = -inf = -1e12) have K = 0 and keep u = v = 0: their outputs are the -1e12 stand-ins either way.  If a sum
   // leaves the normal range (score ranges beyond ~80) the matrix is redone in the log domain below.
+  // The scaling form keeps ONE side row or column per wave in registers (ks): it serves matrices of at most
+  // SK_MAIN + SK_SIDE = 132 padded rows and columns.  Larger ones (up to SK_MAXD) iterate in the log domain below, whose side
+  // loops stride over all remaining rows / columns.
   bool scaled = false;
-  if (scaling_form && iters > 0) {
+  if (scaling_form && iters > 0 && R <= SK_MAIN + SK_SIDE && C <= SK_MAIN + SK_SIDE) {
     float kr[SK_PER], kc[SK_PER];
     constexpr int NSIDE = (SK_MAXD + WAVE - 1) / WAVE;  // elements per lane of a row / column reduced by a whole wave
     float ks[NSIDE];                                    // wave 0: the side row's K, wave 1: the side column's
     bool bad = false;
-    static_assert(SK_MAXD - SK_MAIN <= 2 * (SK_T / WAVE), "one side row per wave");
+    static_assert(2 * SK_SIDE == SK_T / WAVE && SK_MAIN + SK_SIDE <= SK_MAXD, "one side row per even wave, one side column per odd wave");
     const bool row_ok = idx < R && (idx >= M || !rm || rm[idx]);
     const bool col_ok = idx < C && (idx >= N || !cm || cm[idx]);
     // rows / columns beyond the 128 that own four lanes (the dustbins at the demo shape): side row r_side by wave

@@ -345,7 +345,8 @@ int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewm
  * gr_corr_matrix             .../point_matching.py:32-66 == local_global_registration.py:49-83
  *                            (compute_correspondence_matrix on exp(score_mat), use_dustbin=False):
  *                            corr_mat (batch,k1,k2) uint8; *h_num_corr (optional) = number of true
- *                            entries (synchronises when non-null).
+ *                            entries (synchronises when non-null).  Equal values inside a line: the top-k takes
+ *                            the lowest indices (torch.topk leaves the order of ties open).
  * gr_corr_gather             .../point_matching.py:107-113: torch.nonzero order gathers; outputs sized by
  *                            the count gr_corr_matrix returned; `ws` must be the buffer used there.
  * gr_point_to_node_partition geotransformer/modules/ops/pointcloud_partition.py:61-111 (return_count=False):
@@ -356,7 +357,9 @@ int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewm
  * LearnableLogOptimalTransport.forward: scores (batch,m,n), masks uint8 (null = all valid), alpha read
  * from DEVICE memory (the module's learnable parameter), out (batch, m+1, n+1) -- or, with drop_dustbin != 0,
  * (batch, m, n): the matrix without its dustbin row and column, which is all GaussReg keeps (model.py:197-198).  `workspace`: device
- * scratch of gr_sinkhorn_workspace_bytes(batch) (the work list of matrices too large for the one-wave kernel). */
+ * scratch of gr_sinkhorn_workspace_bytes(batch) (the work list of matrices too large for the one-wave kernel).
+ * m, n <= 143.  Matrices of more than 131 rows or columns run every iteration as logsumexp (like those whose score range
+ * leaves fp32's exponent range): same result, several times the time of the scaling form that serves the 128-slot patches. */
 size_t gr_sinkhorn_workspace_bytes(int64_t batch);
 int gr_sinkhorn(const float* scores, int64_t batch, int64_t m, int64_t n, const uint8_t* row_masks,
                 const uint8_t* col_masks, const float* alpha_dev, int num_iterations, float inf, int drop_dustbin,

@@ -4,41 +4,14 @@ column and half-iteration), restated in float64 NumPy, against the log-domain it
 Masked rows / columns (-1e12 stand-ins) are excluded from the comparison as in the GPU tests."""
 import numpy as np
 
-
-def _padded(scores, rm, cm, alpha, inf):
-    B, M, N = scores.shape
-    P = np.full((B, M + 1, N + 1), alpha, np.float64)
-    P[:, :M, :N] = scores
-    prm = np.zeros((B, M + 1), bool)
-    prm[:, :M] = ~rm
-    pcm = np.zeros((B, N + 1), bool)
-    pcm[:, :N] = ~cm
-    P[prm[:, :, None] | pcm[:, None, :]] = -inf
-    nvr, nvc = rm.sum(1).astype(np.float64), cm.sum(1).astype(np.float64)
-    norm = -np.log(nvr + nvc)
-    log_mu = np.empty((B, M + 1))
-    log_mu[:, :M] = norm[:, None]
-    log_mu[:, M] = np.log(nvc) + norm
-    log_nu = np.empty((B, N + 1))
-    log_nu[:, :N] = norm[:, None]
-    log_nu[:, N] = np.log(nvr) + norm
-    return P, prm, pcm, log_mu, log_nu, norm
-
-
-def _lse(x, axis):
-    m = x.max(axis=axis, keepdims=True)
-    return (m + np.log(np.exp(x - m).sum(axis=axis, keepdims=True))).squeeze(axis)
+from fine_matching_f64 import padded as _padded
+from fine_matching_f64 import padded_masks, sinkhorn
 
 
 def log_domain(scores, rm, cm, alpha=1.0, iters=100, inf=1e12):
-    P, prm, pcm, log_mu, log_nu, norm = _padded(scores, rm, cm, alpha, inf)
-    log_mu = np.where(prm, -inf, log_mu)
-    log_nu = np.where(pcm, -inf, log_nu)
-    u, v = np.zeros_like(log_mu), np.zeros_like(log_nu)
-    for _ in range(iters):
-        u = log_mu - _lse(P + v[:, None, :], 2)
-        v = log_nu - _lse(P + u[:, :, None], 1)
-    return P + u[:, :, None] + v[:, None, :] - norm[:, None, None], prm, pcm
+    """The reference's iteration in float64 (tests/fine_matching_f64.py), with the padded masks."""
+    prm, pcm = padded_masks(rm, cm)
+    return sinkhorn(scores, rm, cm, alpha, iters, inf), prm, pcm
 
 
 def scaling_form(scores, rm, cm, alpha=1.0, iters=100, inf=1e12):
