@@ -310,9 +310,11 @@ __global__ __launch_bounds__(256) void full_keys_kernel(int64_t n, const float4*
 //            (many views: the scatter scans the tile counts it builds anyway and writes its own row of seg_off)
 //   scatter  a workgroup owns a chunk; wave w owns a quarter of its Gaussians and a private cursor per tile in LDS
 //            (segment start + the earlier waves' counts).  64 Gaussians (lanes) per step:
-//              small rectangles (<= 8 x 8 tiles, wave-uniform test): with M = 2 / 4 / 8 >= the largest side, a rectangle
-//                holds at most ONE tile of every residue class (x mod M, y mod M), so the wave walks the M*M classes and
-//                in each every lane issues the (at most one) tile it has there.  A given tile is therefore requested by
+//              small rectangles (<= 8 x 8 tiles, wave-uniform test): with Mx = the largest width and My = the largest height
+//                in the wave, a rectangle holds at most ONE tile of every residue class (x mod Mx, y mod My), so the wave
+//                walks the Mx*My classes and in each every lane issues the (at most one) tile it has there (the exact
+//                moduli, not a power of two: most steps of a 640 x 480 frame are 3 x 3 or 3 x 2, nine or six rounds instead
+//                of sixteen).  A given tile is therefore requested by
 //                all its Gaussians in the SAME instruction, and LANE_ORDERED (one ds_add_rtn_u32; equal-address lanes
 //                served in lane order -- probed on the device, see below) hands them consecutive slots in lane = depth
 //                order.  Without that property the lanes of a tile find each other with one ballot per tile-id bit and
@@ -344,6 +346,31 @@ inline bool bin_scans_self(int nchunk, int V) { return !(nchunk <= SCAN_SINGLE_R
 // 640 x 480, 32 views: 4 / 5 / 6 / 8 -> 308 / 306 / 278 / 370 us; at 6, 2 % of the chunks take the direct path)
 constexpr int SCATTER_WGS = 6;
 constexpr int WIDE_T = 1024;  // threads per scatter workgroup for a few views per call
+
+// n mod d for n < 256, 1 <= d <= 8, exact: with m = floor(2^15 / d) + 1 the error m d - 2^15 is at most d, and
+// 255 * 8 < 2^15, so (n m) >> 15 = floor(n / d).  The eight 16-bit multipliers sit in two literals (d wave-uniform:
+// scalar selects, no division; d a constant: folded).
+__device__ __forceinline__ constexpr int mod_small(int n, int d) {
+  const unsigned long long tab = d <= 4 ? 0x2001'2aab'4001'8001ull : 0x1001'124a'1556'199aull;
+  const unsigned int m = (unsigned int)(tab >> (((d - 1) & 3) * 16)) & 0xffffu;
+  return n - (int)(((unsigned int)n * m) >> 15) * d;
+}
+static_assert(mod_small(255, 7) == 255 % 7 && mod_small(254, 3) == 254 % 3 && mod_small(250, 5) == 0 &&
+              mod_small(251, 6) == 251 % 6 && mod_small(255, 8) == 7 && mod_small(200, 1) == 0, "mod_small multipliers");
+// calls f(integral_constant<int, mx>) for the wave-uniform mx in 1 .. 8
+template <typename F>
+__device__ __forceinline__ void by_modulus(int mx, F&& f) {
+  switch (mx) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    case 7: f(std::integral_constant<int, 7>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+  }
+}
 
 __global__ __launch_bounds__(BIN_T) void tile_count_kernel(int P, int V, int gx, int gy, int nchunk,
                                                            const int32_t* __restrict__ nvis,
@@ -662,30 +689,30 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
     const uint32_t r = rr[j];
     int x0 = 0, y0 = 0, w = 0, h = 0;
     if (r != 0u && !rect_decode(r, ii[j], vbase, rec, gx, gy, x0, y0, w, h)) w = h = 0;
-    const int maxd = wave_max_i32_dpp(max(w, h));
+    // the moduli of the step, as in phase C: the largest width and the largest height among the wave's rectangles
+    const int Mx = wave_max_i32_dpp(w), My = wave_max_i32_dpp(h);
     auto cwalk = [&](auto mtag) {
-      constexpr int M = decltype(mtag)::value;
-#pragma unroll
-      for (int ry = 0; ry < M; ++ry) {
-        const int dy = (ry - y0) & (M - 1);
+      constexpr int MX = decltype(mtag)::value;
+      const int x0m = mod_small(x0, MX), y0m = mod_small(y0, My);
+#pragma unroll 1
+      for (int ry = 0; ry < My; ++ry) {
+        int dy = ry - y0m;
+        dy += dy < 0 ? My : 0;
         const int rowbase = (y0 + dy) * gx + x0;
 #pragma unroll
-        for (int rx = 0; rx < M; ++rx) {
-          const int dx = (rx - x0) & (M - 1);
+        for (int rx = 0; rx < MX; ++rx) {
+          int dx = rx - x0m;
+          dx += dx < 0 ? MX : 0;
           if (dy < h && dx < w) count(rowbase + dx);
         }
       }
     };
-    if (maxd == 0) continue;
-    if (TT == WIDE_T) {  // (one camera: the walk measured slower there, 5 390 -> 5 260 views/s)
+    if (Mx == 0) continue;  // (a live rectangle has w > 0 and h > 0)
+    if (TT == WIDE_T || max(Mx, My) > 8) {  // (one camera: the walk measured slower there, 5 390 -> 5 260 views/s)
       for (int y = y0; y < y0 + h; ++y)
         for (int x = x0; x < x0 + w; ++x) count(y * gx + x);
-    } else if (maxd <= 2) cwalk(std::integral_constant<int, 2>{});
-    else if (maxd <= 4) cwalk(std::integral_constant<int, 4>{});
-    else if (maxd <= 8) cwalk(std::integral_constant<int, 8>{});
-    else
-      for (int y = y0; y < y0 + h; ++y)
-        for (int x = x0; x < x0 + w; ++x) count(y * gx + x);
+    } else
+      by_modulus(Mx, cwalk);
   }
   __syncthreads();
   // ---- phase B: counts -> cursors (chunk-local; segment-local for a big chunk)
@@ -742,10 +769,10 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
     else point_list[seg[tile] + pos] = val;
   };
   // LANE_ORDERED: one ds_add_rtn_u32 on the word of the tile's cursor; the other half of the word is another tile's
-  auto bump = [&](unsigned int tile) -> unsigned int {
-    const unsigned int sh = (tile & 1u) * 16u;
-    return (atomicAdd(&myw[tile >> 1], 1u << sh) >> sh) & 0xffffu;
+  auto bump_raw = [&](unsigned int tile) -> unsigned int {  // the whole word: the tile's cursor is half (tile & 1) of it
+    return atomicAdd(&myw[tile >> 1], 1u << ((tile & 1u) * 16u));
   };
+  auto bump = [&](unsigned int tile) -> unsigned int { return (bump_raw(tile) >> ((tile & 1u) * 16u)) & 0xffffu; };
   const unsigned long long lt = (1ull << lane) - 1ull;
   // (rolled: the body is large; the preloaded values move down one register per step instead of being indexed)
 #pragma unroll 1
@@ -762,33 +789,49 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
     if (r_now != 0u && !rect_decode(r_now, id, vbase, rec, gx, gy, x0, y0, w, h)) w = h = 0;
     unsigned long long live = __ballot(w * h != 0);
     if (live == 0ull) continue;
-    const int maxd = wave_max_i32_dpp(max(w, h));
+    const int Mx = wave_max_i32_dpp(w), My = wave_max_i32_dpp(h);
+    const int maxd = max(Mx, My);
     if (maxd <= 8) {
-      // all requests of a row of residue classes are issued before the first returned slot is used: M LDS atomics in
+      // The classes are (x mod Mx, y mod My) with the step's exact moduli: the row of Mx classes is a template instance
+      // (pos / act stay in registers), the My rows are a rolled loop.
+      // all requests of a row of residue classes are issued before the first returned slot is used: Mx LDS atomics in
       // flight instead of one round trip per class (a wave's LDS instructions still execute in issue order)
       auto walk = [&](auto mtag) {
-        constexpr int M = decltype(mtag)::value;
-#pragma unroll
-        for (int ry = 0; ry < M; ++ry) {
-          const int dy = (ry - y0) & (M - 1);
+        constexpr int MX = decltype(mtag)::value;
+        const int x0m = mod_small(x0, MX), y0m = mod_small(y0, My);
+        auto dx_of = [&](int rx) {
+          const int d = rx - x0m;
+          return d + (d < 0 ? MX : 0);
+        };
+#pragma unroll 1
+        for (int ry = 0; ry < My; ++ry) {
+          int dy = ry - y0m;
+          dy += dy < 0 ? My : 0;
           const int rowbase = (y0 + dy) * gx + x0;
           const bool vy = dy < h;
           if (LANE_ORDERED) {
-            unsigned int pos[M];
-            bool act[M];
+            // the first loop only issues: the slot is cut out of the returned word in the second one -- with the shift and
+            // mask next to the atomic the compiler waits for every atomic where it is issued (s_waitcnt lgkmcnt(0) + v_bfe
+            // under the same exec mask), one LDS round trip per class
+            unsigned int raw[MX];
+            bool act[MX];
+            const int wrow = vy ? w : 0;
 #pragma unroll
-            for (int rx = 0; rx < M; ++rx) {
-              const int dx = (rx - x0) & (M - 1);
-              act[rx] = vy && dx < w;
-              pos[rx] = 0u;
-              if (act[rx]) pos[rx] = bump((unsigned int)(rowbase + dx));
+            for (int rx = 0; rx < MX; ++rx) {
+              const int dx = dx_of(rx);
+              act[rx] = dx < wrow;
+              raw[rx] = 0u;
+              if (act[rx]) raw[rx] = bump_raw((unsigned int)(rowbase + dx));
             }
 #pragma unroll
-            for (int rx = 0; rx < M; ++rx)
-              if (act[rx]) put((unsigned int)(rowbase + ((rx - x0) & (M - 1))), pos[rx], t - c * BIN_CHUNK, id);
+            for (int rx = 0; rx < MX; ++rx)
+              if (act[rx]) {
+                const unsigned int tile = (unsigned int)(rowbase + dx_of(rx));
+                put(tile, (raw[rx] >> ((tile & 1u) * 16u)) & 0xffffu, t - c * BIN_CHUNK, id);
+              }
           } else {
-            for (int rx = 0; rx < M; ++rx) {
-              const int dx = (rx - x0) & (M - 1);
+            for (int rx = 0; rx < MX; ++rx) {
+              const int dx = dx_of(rx);
               const bool act = vy && dx < w;
               const unsigned int tile = (unsigned int)(rowbase + dx);
               unsigned long long peers = __ballot(act);
@@ -810,7 +853,7 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
           }
         }
       };
-      // Rectangles of 5 .. 8 tiles a side (large images): the 8 x 8 residue walk issues 64 rounds with a seventh of the lanes
+      // Rectangles of 5 .. 8 tiles a side (large images): the residue walk issues 25 .. 64 rounds with a seventh of the lanes
       // active.  Instead every lane lists its own tiles (owner lane << 16 | tile) at its offset in a per-wave LDS list, and the
       // wave then works through the list with all lanes busy: lane i of a round holds instance i -- instances are in (owner,
       // tile) order, so the lanes of one atomic still arrive at a tile's cursor in depth order.
@@ -820,9 +863,7 @@ __global__ __launch_bounds__(TT) void tile_scatter_kernel(int P, int V, int gx, 
         inc_inst = wave_incl_scan_add_dpp(n_inst);
         t_inst = __builtin_amdgcn_readlane(inc_inst, WAVE - 1);
       }
-      if (maxd <= 2) walk(std::integral_constant<int, 2>{});
-      else if (maxd <= 4) walk(std::integral_constant<int, 4>{});
-      else if (t_inst > elist_cap) walk(std::integral_constant<int, 8>{});
+      if (t_inst > elist_cap) by_modulus(Mx, walk);  // (sides <= 4, or no list / a step that does not fit it)
       else {
         {
           unsigned int* dst = elist + (inc_inst - n_inst);
