@@ -37,7 +37,7 @@ def _stale(out, deps):
 def build(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
-    headers.append(os.path.join(HERE, "..", "include", "gaussreg_hip.h"))
+    headers += [os.path.join(HERE, "..", "include", h) for h in ("gaussreg_hip.h", "gaussreg_hip_train.h")]
     jobs = []
     objs = []
     for src in sources():

@@ -4,10 +4,12 @@ geotransformer/modules/transformer/positional_embedding.py:8-34 (SinusoidalPosit
 reference's (`embedding.div_term` is a buffer, `proj_d.{weight,bias}`, `proj_a.{weight,bias}`).
 
 Inference by default.  Inside `gaussreg_amd.kpconv.differentiable()` the forward is the same kernel (the same values) inside
-an autograd Function whose backward gives `proj_d` and `proj_a` their gradients: it recomputes the reference composition
-(indices, sinusoids, the two Linears, max / mean over angle_k) in torch, a chunk of rows at a time, and differentiates
-each chunk against its rows of the upstream (N,N,C) gradient.  Once per cloud and step, not once per layer.  Points get no
-gradient."""
+an autograd Function whose backward gives `proj_d` and `proj_a` their gradients from `gr_geo_embedding_backward`
+(gaussreg_amd/csrc/geo_embedding_backward.hip): it re-walks the forward's pairs with the forward's own device code
+(neighbour sets and indices bit for bit the forward's) and forms the two (C x C) weight gradients as fp32-MFMA products
+against sinusoid rows generated on the fly; one call per cloud, the clouds of a batch accumulated in index order.  Once per
+cloud and step, not once per layer.  `GeometricStructureEmbedding.grad_impl = "torch"` (or a hidden_dim that is no multiple
+of 32) selects the older chunked torch recomputation, `_projection_grads`.  Points get no gradient."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -24,13 +26,14 @@ def _sinusoid(idx, div):
 
 
 def _projection_grads(p, go, wd, bd, wa, ba, div, sigma_d, factor_a, k, mean):
-    """One cloud: p (N,3), go (N,N,C) -> the gradients of out = proj_d(sin(d_idx)) + reduce_k proj_a(sin(a_idx)) with
+    """The fallback of the backward (`grad_impl = "torch"`, or hidden_dim % 32 != 0).
+    One cloud: p (N,3), go (N,N,C) -> the gradients of out = proj_d(sin(d_idx)) + reduce_k proj_a(sin(a_idx)) with
     respect to (wd, bd, wa, ba), float32.  The indices follow geotransformer.py:38-53 with the kernel's neighbour rule
     (ascending distance, lowest index first, the first entry dropped); rows are taken in ascending chunks.
     The distances and the neighbour sets are RECOMPUTED here in torch fp32, not taken from the forward kernel: where two
     neighbours are equidistant within fp32 rounding, or a point's distance to itself does not round to exactly 0, this may
-    pick another neighbour than the forward did and so differentiate a slightly different function (DESIGN.md 3.5.2,
-    Known gap 12).  On clouds whose distances are exact in fp32 both sides agree."""
+    pick another neighbour than the forward did and so differentiate a slightly different function; the
+    HIP backward has no such limitation.  On clouds whose distances are exact in fp32 both sides agree."""
     N, C = p.shape[0], wd.shape[0]
     leaves = [t.detach().clone().requires_grad_(True) for t in (wd, bd, wa, ba)]
     grads = [torch.zeros_like(t) for t in leaves]
@@ -65,13 +68,38 @@ def _projection_grads(p, go, wd, bd, wa, ba, div, sigma_d, factor_a, k, mean):
     return grads
 
 
+def _hip_projection_grads(m, p, go, wa, ba, div, table_a):
+    """p (B,N,3), go (B,N,N,C) on the GPU -> [grad_wd, grad_bd, grad_wa, grad_ba], float32, summed over the batch by the
+    kernel itself (accumulate = b > 0: cloud 0 writes, the others add, in index order)."""
+    dev = p.device
+    (B, N, _), C, k = p.shape, go.shape[-1], int(m.angle_k)
+    shapes = ((C, C), (C,), (C, C), (C,))
+    if B == 0:
+        return [torch.zeros(s, dtype=torch.float32, device=dev) for s in shapes]
+    gwd, gbd, gwa, gba = (torch.empty(s, dtype=torch.float32, device=dev) for s in shapes)
+    nbytes = _lib.lib().gr_geo_embedding_backward_workspace_bytes(N, C, k)
+    rows = 0 if table_a is None else table_a.shape[0]
+    for b in range(B):
+        _lib.call(dev, "gr_geo_embedding_backward", p[b], N, go[b], table_a, rows, float(m.TABLE_INV_H), wa, ba, div, C,
+                  float(m.sigma_d), float(m.factor_a), k, 1 if m.reduction_a == 'mean' else 0, int(b > 0),
+                  gwd, gbd, gwa, gba, ws=nbytes)
+    return [gwd, gbd, gwa, gba]
+
+
 class _GeoEmbeddingFunction(torch.autograd.Function):
-    """Forward: the HIP kernel, whichever mode the module is in.  Backward: _projection_grads per cloud."""
+    """Forward: the HIP kernel, whichever mode the module is in.  Backward: gr_geo_embedding_backward per cloud
+    (`grad_impl == "hip"`, hidden_dim % 32 == 0), else _projection_grads per cloud."""
 
     @staticmethod
     def forward(ctx, module, points, wd, bd, wa, ba):
         out = module._forward_kernel(points)
         ctx.module = module
+        ctx.hip = module._hip_backward()
+        ctx.table_a = None
+        if ctx.hip and module.reduction_a == 'max' and int(module.angle_k) > 0:
+            # the 'max' winners come from the F_a table of THESE weights: the one the table-mode forward has just used; the
+            # gemm modes build it here on demand (cached like the forward's; inference tensors rebuild every call)
+            ctx.table_a = module._function_tables(out.device if out.is_cuda else _lib.require_gpu())[1]
         ctx.save_for_backward(points, wd, bd, wa, ba)
         return out
 
@@ -82,13 +110,16 @@ class _GeoEmbeddingFunction(torch.autograd.Function):
         dev = grad_out.device if grad_out.is_cuda else _lib.require_gpu()
         f = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
         go, p, div = f(grad_out), f(points), f(m.embedding.div_term)
-        total = None
-        for b in range(p.shape[0]):
-            g = _projection_grads(p[b], go[b], f(wd), f(bd), f(wa), f(ba), div, float(m.sigma_d), float(m.factor_a),
-                                  int(m.angle_k), m.reduction_a == 'mean')
-            total = g if total is None else [t + x for t, x in zip(total, g)]
-        if total is None:
-            total = [torch.zeros_like(f(t)) for t in (wd, bd, wa, ba)]
+        if ctx.hip:
+            total = _hip_projection_grads(m, p, go, f(wa), f(ba), div, ctx.table_a)
+        else:
+            total = None
+            for b in range(p.shape[0]):
+                g = _projection_grads(p[b], go[b], f(wd), f(bd), f(wa), f(ba), div, float(m.sigma_d), float(m.factor_a),
+                                      int(m.angle_k), m.reduction_a == 'mean')
+                total = g if total is None else [t + x for t, x in zip(total, g)]
+            if total is None:
+                total = [torch.zeros_like(f(t)) for t in (wd, bd, wa, ba)]
         grads = [t.to(device=w.device, dtype=w.dtype) for t, w in zip(total, (wd, bd, wa, ba))]
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
 
@@ -114,6 +145,7 @@ class SinusoidalPositionalEmbedding(nn.Module):
 class GeometricStructureEmbedding(nn.Module):
     TABLE_INV_H = 32.0        # table step 1/32 of an embedding index: interpolation error ~ 2e-8
     TABLE_X_MAX_D = 256.0     # distance indices up to 256 (= 51 m at sigma_d 0.2) come from the table, beyond: direct evaluation
+    grad_impl = "hip"         # the backward inside differentiable(): "hip" (gr_geo_embedding_backward) or "torch" (_projection_grads)
 
     def __init__(self, hidden_dim, sigma_d, sigma_a, angle_k, reduction_a='max', fp32_mfma=False, mode="table"):
         """mode="table" (default): the two projections are tabulated as functions of their scalar index once per set of
@@ -158,9 +190,17 @@ class GeometricStructureEmbedding(nn.Module):
             self._tables = (stamp, table(self.proj_d, self.TABLE_X_MAX_D), table(self.proj_a, x_max_a))
         return self._tables[1], self._tables[2]
 
+    def _hip_backward(self):
+        """Which backward `differentiable()` uses: the HIP kernel needs hidden_dim % 32 == 0 (its MFMA slabs); any other
+        width takes the torch recomputation, as `grad_impl = "torch"` does."""
+        if self.grad_impl not in ("hip", "torch"):
+            raise ValueError("grad_impl must be 'hip' or 'torch'")
+        return self.grad_impl == "hip" and self.proj_d.weight.shape[0] % 32 == 0
+
     def forward(self, points):
         """points (B, N, 3) -> embeddings (B, N, N, hidden_dim), geotransformer.py:57-73.  Inside `differentiable()` the
-        result carries the gradient of proj_d / proj_a; points that require grad raise ValueError."""
+        result carries the gradient of proj_d / proj_a (HIP backward: gr_geo_embedding_backward, see `grad_impl`); points
+        that require grad raise ValueError."""
         if differentiable_active():
             if points.requires_grad:
                 raise ValueError("points require grad, but the structure embedding has no gradient with respect to the points")

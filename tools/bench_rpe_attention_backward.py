@@ -3,7 +3,9 @@ GeometricTransformer (hidden 256, 4 heads, self / cross x 3, angle_k 3, 'max'): 
 gaussreg_amd.kpconv.differentiable() against the reference's composition in stock torch fp32 with autograd, on the same
 GPU in the same process, alternating; peak allocated memory of each.  The row pass of the backward is also reported as a
 fraction of HBM peak against the bytes it must move (one embedding read, plus one write when grad_embed is wanted), from
-the library's per-kernel event timing.
+the library's per-kernel event timing.  Per cloud, the structure embedding's backward alone: the HIP kernel against the
+torch recomputation (`grad_impl`), its kernel time and share of the fp32 MFMA peak, peak memory, and how far the two paths'
+gradients are apart.
 
     python tools/bench_rpe_attention_backward.py [--reps 7] [--n 767] [--skip-stack]
 """
@@ -194,9 +196,31 @@ if not args.skip_stack:
     print(f"GeometricTransformer, two clouds of {N}, hidden {C}, {H} heads, {blocks}")
     for name, t, fn in zip(["HIP forward", "HIP fwd+bwd", "torch fwd+bwd"], ts, [hip_stack_forward, hip_stack, torch_stack]):
         print(f"  {name:28s} {t:8.2f} ms   peak {peak_mb(fn):8.1f} MB")
-    emb_mod = model.embedding
-    with differentiable():
-        e = emb_mod(p0)
-    ge = torch.randn_like(e)
-    t_emb = alternate([lambda: torch.autograd.grad(e, list(emb_mod.parameters()), ge, retain_graph=True)], 3)[0]
-    print(f"  structure embedding backward (torch recomputation, one cloud) {t_emb:8.2f} ms")
+    # ---- the structure embedding's backward alone, per cloud: the HIP kernel against the torch recomputation
+    # (GeometricStructureEmbedding.grad_impl), alternating; the path is chosen when the forward builds the graph
+    from gaussreg_amd.embedding import GeometricStructureEmbedding
+    FP32_MFMA_PEAK = 157.3e12
+    k = model.embedding.angle_k
+    for red in ("max", "mean"):
+        emb_mod = GeometricStructureEmbedding(C, 0.2, 15, k, reduction_a=red).cuda()
+        emb_mod.load_state_dict(model.embedding.state_dict())
+        params = list(emb_mod.parameters())
+        graphs = {}
+        for impl in ("hip", "torch"):
+            emb_mod.grad_impl = impl
+            with differentiable():
+                graphs[impl] = emb_mod(p0)
+        emb_mod.grad_impl = "hip"
+        ge = torch.randn_like(graphs["hip"])
+        run = {impl: (lambda e=e: torch.autograd.grad(e, params, ge, retain_graph=True)) for impl, e in graphs.items()}
+        t_hip, t_torch = alternate([run["hip"], run["torch"]], max(3, args.reps // 2))
+        ms = kernel_ms(run["hip"], "geo_embedding_backward")
+        flop = 2.0 * N * N * C * C * (1 + (k if red == "max" else 1))
+        g_hip, g_torch = run["hip"](), run["torch"]()
+        rel = max(((a - b).abs().max() / b.abs().max()).item() for a, b in zip(g_hip, g_torch))
+        print(f"  structure embedding backward, one cloud, '{red}': HIP {t_hip:8.3f} ms (peak {peak_mb(run['hip']):7.1f} MB)   "
+              f"torch recomputation {t_torch:8.2f} ms (peak {peak_mb(run['torch']):7.1f} MB)")
+        print(f"    kernels (GEMM + reduction) {ms:8.3f} ms = {flop / 1e9:.0f} GFLOP at {flop / (ms * 1e-3) / 1e12:.1f} TFLOP/s = "
+              f"{100 * flop / (ms * 1e-3) / FP32_MFMA_PEAK:.0f} % of the fp32 MFMA peak; largest relative difference of the two "
+              f"paths' gradients {rel:.2e}")
+        del graphs, run, ge, g_hip, g_torch
