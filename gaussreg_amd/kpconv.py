@@ -228,28 +228,16 @@ class KPConv(nn.Module):
             self._kernel_points_ready = True
         return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
+    @no_grad_unless_differentiable
     def forward(self, s_feats, q_points, s_points, neighbor_indices):
+        """Inside `differentiable()` the same kernels run through one autograd Function; the conversions around it are torch
+        ops with their own grad."""
         if not self._kernel_points_ready:
             raise RuntimeError("KPConv.kernel_points is uninitialised: no stored disposition for kernel_size=%d; pass "
                                "kernel_points= or load a state dict that carries them" % self.kernel_size)
-        if differentiable_active():
-            return self._forward_differentiable(s_feats, q_points, s_points, neighbor_indices)
-        with torch.no_grad():
-            dev = _lib.require_gpu()
-            out_device = s_feats.device
-            f = _lib.to_device(s_feats, dev, torch.float32)
-            dev = f.device
-            q, s = _lib.to_device(q_points, dev, torch.float32), _lib.to_device(s_points, dev, torch.float32)
-            nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
-            kp = _lib.to_device(self.kernel_points, dev, torch.float32)
-            wts = _lib.to_device(self.weights.detach(), dev, torch.float32)
-            b = None if self.bias is None else _lib.to_device(self.bias.detach(), dev, torch.float32)
-            out = _kpconv_forward(f, q, s, nb, kp, wts, b, self.sigma, self.inf)
-            return _lib.like_input(out, out_device)
-
-    def _forward_differentiable(self, s_feats, q_points, s_points, neighbor_indices):
-        """The same kernels through one autograd Function; the conversions around it are torch ops with their own grad."""
-        _no_point_grad(q_points=q_points, s_points=s_points)
+        train = differentiable_active()
+        if train:
+            _no_point_grad(q_points=q_points, s_points=s_points)
         dev = _lib.require_gpu()
         out_device = s_feats.device
         f = _lib.to_device(s_feats, dev, torch.float32)
@@ -259,7 +247,10 @@ class KPConv(nn.Module):
         kp = _lib.to_device(self.kernel_points, dev, torch.float32)
         wts = _lib.to_device(self.weights, dev, torch.float32)
         b = None if self.bias is None else _lib.to_device(self.bias, dev, torch.float32)
-        out = _KPConvFunction.apply(f, wts, b, q, s, nb, kp, float(self.sigma), float(self.inf), _mode.state[1])
+        if train:
+            out = _KPConvFunction.apply(f, wts, b, q, s, nb, kp, float(self.sigma), float(self.inf), _mode.state[1])
+        else:
+            out = _kpconv_forward(f, q, s, nb, kp, wts, b, self.sigma, self.inf)
         return _lib.like_input(out, out_device)
 
 
@@ -273,32 +264,23 @@ def _pool_forward(xx, nb, mode):
     return out
 
 
+@no_grad_unless_differentiable
 def _pool(x, neighbor_indices, mode):
     dev = _lib.require_gpu()
     out_device = x.device
     xx = _lib.to_device(x, dev, torch.float32)
     dev = xx.device
     nb = neighbor_indices.to(device=dev, dtype=torch.int64).contiguous()
-    if differentiable_active():
-        out = _PoolFunction.apply(xx, nb, mode)
-    else:
-        with torch.no_grad():
-            out = _pool_forward(xx, nb, mode)
+    out = _PoolFunction.apply(xx, nb, mode) if differentiable_active() else _pool_forward(xx, nb, mode)
     return _lib.like_input(out, out_device)
 
 
 def maxpool(x, neighbor_indices):
     """kpconv/functional.py:54-67.  Inside `differentiable()` the gradient goes to the neighbour row that attained the
     maximum (the lowest column on a tie; dropped where the zero shadow row won)."""
-    if differentiable_active():
-        return _pool(x, neighbor_indices, 0)
-    with torch.no_grad():
-        return _pool(x, neighbor_indices, 0)
+    return _pool(x, neighbor_indices, 0)
 
 
 def nearest_upsample(x, upsample_indices):
     """kpconv/functional.py:6-22 (only the first neighbour column is used)."""
-    if differentiable_active():
-        return _pool(x, upsample_indices, 1)
-    with torch.no_grad():
-        return _pool(x, upsample_indices, 1)
+    return _pool(x, upsample_indices, 1)

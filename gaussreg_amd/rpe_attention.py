@@ -1,11 +1,11 @@
 """Mirror of geotransformer/modules/transformer/rpe_transformer.py:18-72 (RPEMultiHeadAttention) -- inference by default,
-with autograd (HIP backward, csrc/rpe_attention_backward.hip) inside `gaussreg_amd.kpconv.differentiable()`.
+with autograd (HIP backward, same source file as the forward: csrc/rpe_attention.hip) inside `gaussreg_amd.kpconv.differentiable()`.
 
 The reference projects the (B,N,M,C) relative-position embedding through `proj_p` in every layer (77 GFLOP and a
 602 MB temporary at N=M=767, C=256) before contracting it with q.  The contraction is linear in the embedding, so it
 is re-associated here:  s_p[h,n,m] = emb[n,m,:] . (W_p[h]^T q[h,n,:]) + q[h,n,:] . b_p[h], and everything after the four
 input projections -- q k^T, the positional term, scaling, factors / weights / masks, softmax and scores @ v -- runs in ONE
-HIP kernel per batch element (gaussreg_amd/csrc/geo_embedding.hip: gr_rpe_attention): the embedding is streamed exactly
+HIP kernel per batch element (gaussreg_amd/csrc/rpe_attention.hip: gr_rpe_attention): the embedding is streamed exactly
 once per layer and no (H,N,M) or (N,M,C) intermediate goes through HBM.  The projections (nn.Linear) and the tiny
 u = W_p^T q product stay torch ops.  State-dict keys are the reference's.
 
@@ -20,15 +20,16 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from .kpconv import differentiable_active
+from .kpconv import differentiable_active, no_grad_unless_differentiable
 
 
-def _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H):
-    """gr_rpe_attention on the float32 contiguous tensors of one batch element -> hidden (N,C), scores (H,N,M)."""
+def _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H, scores=None, hidden=None):
+    """gr_rpe_attention on the float32 contiguous tensors of one batch element -> hidden (N,C), scores (H,N,M), written into
+    the caller's tensors where it passes them."""
     dev = q2.device
     (N, C), M = q2.shape, k2.shape[0]
-    scores = torch.empty((H, N, M), dtype=torch.float32, device=dev)
-    hidden = torch.empty((N, C), dtype=torch.float32, device=dev)
+    scores = torch.empty((H, N, M), dtype=torch.float32, device=dev) if scores is None else scores
+    hidden = torch.empty((N, C), dtype=torch.float32, device=dev) if hidden is None else hidden
     _lib.call(dev, "gr_rpe_attention", emb, u, add, q2, k2, v2, fac, kw, km, N, M, C, H, scores, hidden)
     return hidden, scores
 
@@ -76,6 +77,7 @@ class RPEMultiHeadAttention(nn.Module):
         self.proj_p = nn.Linear(self.d_model, self.d_model)
         self.dropout = nn.Identity() if dropout is None or dropout <= 0 else nn.Dropout(dropout)
 
+    @no_grad_unless_differentiable
     def forward(self, input_q, input_k, input_v, embed_qk, key_weights=None, key_masks=None, attention_factors=None,
                 lengths=None):
         """(B,N,C), (B,M,C), (B,M,C), (B,N,M,C) -> hidden_states (B,N,C), attention_scores (B,H,N,M).
@@ -85,37 +87,89 @@ class RPEMultiHeadAttention(nn.Module):
         fused kernel runs per element with its true size, so the real rows are exactly what the unpadded call returns;
         padded rows of hidden_states are zero, attention_scores is None.
 
-        Inside `differentiable()` (grad mode on) the outputs carry a grad_fn; their values are those of inference."""
-        if differentiable_active():
-            return self._forward_differentiable(input_q, input_k, input_v, embed_qk, key_weights, key_masks,
-                                                attention_factors, lengths)
-        with torch.no_grad():
-            return self._forward_inference(input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors,
-                                           lengths)
-
-    def _forward_inference(self, input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors, lengths):
-        if lengths is not None:
-            return self._forward_ragged(input_q, input_k, input_v, embed_qk, lengths)
+        Inside `differentiable()` (grad mode on) the outputs carry a grad_fn; their values are those of inference: the same
+        projections and the same kernel, the kernel inside _RPEAttentionFunction, everything around it torch ops with their
+        own grad.  What the backward could not do is refused here and not at backward()."""
+        train = differentiable_active()
+        if train:
+            for name, t in (("key_weights", key_weights), ("attention_factors", attention_factors)):
+                if t is not None and t.requires_grad:
+                    raise ValueError(f"{name} requires grad, but the HIP RPE attention has no gradient with respect to it")
+            if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
+                raise NotImplementedError("RPEMultiHeadAttention: dropout on the attention scores is not differentiable here")
         _lib.require_gpu()
         if not input_q.is_cuda:
             raise RuntimeError("RPEMultiHeadAttention: inputs must live on the GPU")
+        if lengths is not None:
+            return self._forward_ragged(input_q, input_k, input_v, embed_qk, lengths, train), None
         dev = input_q.device
         B, N, C = input_q.shape
-        M = input_k.shape[1]
-        H, ch = self.num_heads, self.d_model_per_head
+        M, H = input_k.shape[1], self.num_heads
         emb = embed_qk.to(torch.float32).contiguous()
+        fac, kw, km = (None if t is None else t.to(dtype).contiguous() for t, dtype in
+                       ((attention_factors, torch.float32), (key_weights, torch.float32), (key_masks, torch.uint8)))
+
+        def element(b, **out):
+            # B = 1: a view, whose backward is a view of the (N,M,C) gradient (a select would copy it into zeros)
+            return self._attend(input_q[b], input_k[b], input_v[b], emb.view(N, M, C) if B == 1 else emb[b],
+                                None if fac is None else fac[b], None if kw is None else kw[b],
+                                None if km is None else km[b], **out)
+
+        if train:
+            outs = [element(b) for b in range(B)]
+            if B == 1:
+                return outs[0][0].unsqueeze(0), outs[0][1].unsqueeze(0)
+            return torch.stack([hid for hid, _ in outs]), torch.stack([sc for _, sc in outs])
         scores = torch.empty((B, H, N, M), dtype=torch.float32, device=dev)
         hidden = torch.empty((B, N, C), dtype=torch.float32, device=dev)
-        fac = None if attention_factors is None else attention_factors.to(torch.float32).contiguous()
-        kw = None if key_weights is None else key_weights.to(torch.float32).contiguous()
-        km = None if key_masks is None else key_masks.to(torch.uint8).contiguous()
         for b in range(B):
-            q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
-            _lib.call(dev, "gr_rpe_attention", emb[b], u, add, q2, k2, v2, None if fac is None else fac[b],
-                      None if kw is None else kw[b], None if km is None else km[b], N, M, C, H, scores[b], hidden[b])
+            element(b, scores=scores[b], hidden=hidden[b])
         if not isinstance(self.dropout, nn.Identity):
             scores = self.dropout(scores)  # inference: identity (the reference applies dropout to the scores before @ v)
         return hidden, scores
+
+    def _forward_ragged(self, input_q, input_k, input_v, embed_list, lengths, train):
+        """hidden_states (B,N,C) of a padded stack: element b alone with its lengths[b] rows, zeros below them."""
+        dev = input_q.device
+        B, N, C = input_q.shape
+        if input_k.shape != input_q.shape or len(embed_list) != B or len(lengths) != B:
+            raise ValueError("lengths: self-attention over a padded stack, one embedding per element")
+        lengths = [int(n) for n in lengths]
+
+        def element(b, **out):
+            n, emb = lengths[b], embed_list[b]
+            if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
+                raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
+            if n == 0:
+                return None
+            return self._attend(input_q[b, :n], input_k[b, :n], input_v[b, :n], emb, None, None, None, **out)
+
+        if train:
+            rows = []
+            for b in range(B):
+                out = element(b)                                                  # hidden and its own scores tensor
+                rows.append(torch.zeros((N, C), dtype=torch.float32, device=dev) if out is None
+                            else F.pad(out[0], (0, 0, 0, N - lengths[b])))
+            return torch.stack(rows)
+        hidden = torch.zeros((B, N, C), dtype=torch.float32, device=dev)
+        nmax = max(lengths)
+        scores = torch.empty((self.num_heads, nmax, nmax), dtype=torch.float32, device=dev)   # scratch: written, never read
+        for b in range(B):
+            element(b, scores=scores, hidden=hidden[b])
+        return hidden
+
+    def _attend(self, xq, xk, xv, emb, fac, kw, km, **out):
+        """One batch element: `_project`, then the kernel -- through the autograd Function inside `differentiable()`, else
+        straight into `scores=` / `hidden=`.  -> hidden (n,C), scores (H,n,m)."""
+        H = self.num_heads
+        q2, k2, v2, u, add = self._project(xq, xk, xv)
+        if not differentiable_active():
+            return _attention_forward(emb, u, add, q2, k2, v2, fac, kw, km, H, **out)
+        max_keys = _lib.lib().gr_rpe_attention_backward_max_keys(self.d_model, H)
+        if k2.shape[0] > max_keys:
+            raise RuntimeError("gaussreg_hip: rpe_attention_backward: %d keys x %d heads do not fit in LDS (at most %d keys "
+                               "inside differentiable())" % (k2.shape[0], H, max_keys))
+        return _RPEAttentionFunction.apply(emb, u, add, q2, k2, v2, fac, kw, km, H)
 
     def _project(self, xq, xk, xv):
         """The torch side of ONE batch element, (n,C) / (m,C) / (m,C) matrices: the three input projections (heads side by
@@ -131,80 +185,3 @@ class RPEMultiHeadAttention(nn.Module):
         u = torch.einsum('nhc,hcj->nhj', qh, self.proj_p.weight.view(H, ch, C)).contiguous()   # rows h*ch..: head h
         add = torch.einsum('nhc,hc->nh', qh, self.proj_p.bias.view(H, ch)).contiguous()
         return q2, k2, v2, u, add
-
-    def _forward_differentiable(self, input_q, input_k, input_v, embed_qk, key_weights, key_masks, attention_factors,
-                                lengths):
-        """The same projections and the same kernel, the kernel inside _RPEAttentionFunction; everything around it is torch
-        ops with their own grad.  Refuses what the backward could not do, here and not at backward()."""
-        for name, t in (("key_weights", key_weights), ("attention_factors", attention_factors)):
-            if t is not None and t.requires_grad:
-                raise ValueError(f"{name} requires grad, but the HIP RPE attention has no gradient with respect to it")
-        if isinstance(self.dropout, nn.Dropout) and self.training and self.dropout.p > 0:
-            raise NotImplementedError("RPEMultiHeadAttention: dropout on the attention scores is not differentiable here")
-        _lib.require_gpu()
-        if not input_q.is_cuda:
-            raise RuntimeError("RPEMultiHeadAttention: inputs must live on the GPU")
-        B, N, C = input_q.shape
-        H = self.num_heads
-        max_keys = _lib.lib().gr_rpe_attention_backward_max_keys(C, H)
-        if lengths is not None:
-            if input_k.shape != input_q.shape or len(embed_qk) != B or len(lengths) != B:
-                raise ValueError("lengths: self-attention over a padded stack, one embedding per element")
-            rows = []
-            for b in range(B):
-                n = int(lengths[b])
-                emb = embed_qk[b]
-                if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
-                    raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
-                if n == 0:
-                    rows.append(torch.zeros((N, C), dtype=torch.float32, device=input_q.device))
-                    continue
-                self._check_backward_fits(n, H, max_keys)
-                q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
-                hid, _ = _RPEAttentionFunction.apply(emb, u, add, q2, k2, v2, None, None, None, H)   # its own scores tensor
-                rows.append(F.pad(hid, (0, 0, 0, N - n)))
-            return torch.stack(rows), None
-        M = input_k.shape[1]
-        self._check_backward_fits(M, H, max_keys)
-        emb = embed_qk.to(torch.float32).contiguous()
-        fac = None if attention_factors is None else attention_factors.to(torch.float32).contiguous()
-        kw = None if key_weights is None else key_weights.to(torch.float32).contiguous()
-        km = None if key_masks is None else key_masks.to(torch.uint8).contiguous()
-        hidden, scores = [], []
-        for b in range(B):
-            q2, k2, v2, u, add = self._project(input_q[b], input_k[b], input_v[b])
-            # B = 1: a view, whose backward is a view of the (N,M,C) gradient (a select would copy it into zeros)
-            emb_b = emb.view(N, M, C) if B == 1 else emb[b]
-            hid, sc = _RPEAttentionFunction.apply(emb_b, u, add, q2, k2, v2, None if fac is None else fac[b],
-                                                  None if kw is None else kw[b], None if km is None else km[b], H)
-            hidden.append(hid)
-            scores.append(sc)
-        if B == 1:
-            return hidden[0].unsqueeze(0), scores[0].unsqueeze(0)
-        return torch.stack(hidden), torch.stack(scores)
-
-    @staticmethod
-    def _check_backward_fits(m, heads, max_keys):
-        if m > max_keys:
-            raise RuntimeError("gaussreg_hip: rpe_attention_backward: %d keys x %d heads do not fit in LDS (at most %d keys "
-                               "inside differentiable())" % (m, heads, max_keys))
-
-    def _forward_ragged(self, input_q, input_k, input_v, embed_list, lengths):
-        dev = input_q.device
-        B, N, C = input_q.shape
-        H, ch = self.num_heads, self.d_model_per_head
-        if input_k.shape != input_q.shape or len(embed_list) != B or len(lengths) != B:
-            raise ValueError("lengths: self-attention over a padded stack, one embedding per element")
-        hidden = torch.zeros((B, N, C), dtype=torch.float32, device=dev)
-        nmax = max(int(n) for n in lengths)
-        scores = torch.empty((H, nmax, nmax), dtype=torch.float32, device=dev)   # scratch: the kernel writes it, nobody reads
-        for b in range(B):
-            n = int(lengths[b])
-            emb = embed_list[b]
-            if emb.shape != (n, n, C) or not emb.is_contiguous() or emb.dtype != torch.float32:
-                raise ValueError("embedding %d must be a contiguous float32 (n, n, C) tensor" % b)
-            if n == 0:
-                continue
-            q2, k2, v2, u, add = self._project(input_q[b, :n], input_k[b, :n], input_v[b, :n])
-            _lib.call(dev, "gr_rpe_attention", emb, u, add, q2, k2, v2, None, None, None, n, n, C, H, scores, hidden[b])
-        return hidden, None

@@ -18,7 +18,7 @@ cross-attention has no (N,M,C) stream -- 767 x 767 x 256 is three small GEMMs an
 through torch, like the nn.Linear / nn.LayerNorm glue around both.
 
 Every forward here switches grad off unless `differentiable_active()`.  Inside the context the torch glue is differentiated
-by torch autograd, the RPE attention by its HIP backward (csrc/rpe_attention_backward.hip) and the structure embedding's
+by torch autograd, the RPE attention by its HIP backward (csrc/rpe_attention.hip) and the structure embedding's
 two projections by a chunked torch recomputation (gaussreg_amd.embedding); the forward values are those of inference.
 """
 import torch
