@@ -17,8 +17,14 @@ namespace {
 
 __device__ __forceinline__ float node_point_dist(float4 nd, float px, float py, float pz, float p2) {
   const float xy = fmaf(nd.z, pz, fmaf(nd.y, py, nd.x * px));  // 3-term dot product
-  return fmaxf((nd.w - 2.0f * xy) + p2, 0.0f);
+  const float d = (nd.w - 2.0f * xy) + p2;
+  return d < 0.0f ? 0.0f : d;  // clamp(min=0) as torch does it: NaN stays NaN (fmaxf would turn it into 0, the best distance)
 }
+
+// A member is listed when its distance is finite.  A point with a NaN coordinate has no distance below INFINITY to any node:
+// it keeps bm = 0 and best = INFINITY (torch.min gives such a column index 0 too), its key sorts behind every finite member,
+// and it is never emitted -- the reference's topk puts it behind the 1e12 of the non-members, so it does not list it either.
+__device__ __forceinline__ bool key_listed(unsigned long long key) { return (unsigned)(key >> 32) < 0x7f800000u; }
 
 constexpr int P2N_CHUNK = 1024;  // nodes staged per LDS round
 
@@ -133,7 +139,7 @@ __global__ __launch_bounds__(256) void select_kernel(int n, int K, const int32_t
     // lane j holds the j-th smallest key; outputs past the node's points are padding
     for (int j = lane; j < K; j += WAVE) {
       const unsigned long long kj = j < WAVE ? key : KEY_INF;  // (j < 64 only in the first trip, where j == lane)
-      const bool ok = kj != KEY_INF;
+      const bool ok = key_listed(kj);
       knn_idx[(int64_t)m * K + j] = ok ? (int64_t)((unsigned int)(kj & 0xffffffffull) - (unsigned)pbase) : (int64_t)n;
       knn_mask[(int64_t)m * K + j] = ok ? 1 : 0;
     }
@@ -169,7 +175,7 @@ __global__ __launch_bounds__(256) void select_kernel(int n, int K, const int32_t
   } while (pos < b);
   for (int j = threadIdx.x; j < K; j += 256) {
     const unsigned long long key = sk[j];
-    const bool ok = key != KEY_INF;
+    const bool ok = key_listed(key);
     knn_idx[(int64_t)m * K + j] = ok ? (int64_t)((unsigned int)(key & 0xffffffffull) - (unsigned)pbase) : (int64_t)n;  // :102 pad = N
     knn_mask[(int64_t)m * K + j] = ok ? 1 : 0;                                                      // :101
   }

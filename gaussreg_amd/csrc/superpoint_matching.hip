@@ -125,8 +125,11 @@ __device__ __forceinline__ float pd_distance(float xy, int normalized, const flo
   float d;
   if (normalized) d = 2.0f - 2.0f * xy;      // pairwise_distance.py:26
   else d = (*x2 - 2.0f * xy) + *y2;          // pairwise_distance.py:30
-  d = fmaxf(d, 0.0f);                        // :31 clamp(min=0)
-  if (EPI == EPI_EXPNEG) d = expf(-d);       // superpoint_matching.py:37
+  // :31 clamp(min=0).  The distance output keeps NaN as torch's clamp does (fmaxf returns 0 for it: a NaN feature row came out
+  // as the best possible match of everything).  The exp(-d) epilogue keeps fmaxf: SuperPointMatching's sums and its radix
+  // select are written for finite scores
+  if (EPI == EPI_EXPNEG) d = expf(-fmaxf(d, 0.0f));  // superpoint_matching.py:37
+  else d = d < 0.0f ? 0.0f : d;
   return d;
 }
 

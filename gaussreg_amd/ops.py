@@ -34,6 +34,8 @@ def radius_search(q_points, s_points, q_lengths, s_lengths, radius, neighbor_lim
 
 # ---------------------------------------------------------------------------------------------
 # dense / partition operators (reference: modules/ops/pairwise_distance.py, pointcloud_partition.py)
+import math  # noqa: E402
+
 import torch  # noqa: E402
 
 from . import _lib  # noqa: E402
@@ -47,9 +49,10 @@ def pairwise_distance(x, y, normalized=False, channel_first=False):
     lead = x.shape[:-2]
     if y.shape[:-2] != lead:
         raise RuntimeError("pairwise_distance: x and y must have the same leading (batch) dimensions")
-    xs = _lib.to_device(x, None, torch.float32, "x", cast=False).reshape(-1, x.shape[-2], x.shape[-1])
-    ys = _lib.to_device(y, None, torch.float32, "y", cast=False).reshape(-1, y.shape[-2], y.shape[-1])
-    B, N, C = xs.shape
+    B = math.prod(lead)  # (not reshape(-1, ...): with N = 0 or M = 0 the batch count cannot be inferred)
+    xs = _lib.to_device(x, None, torch.float32, "x", cast=False).reshape(B, x.shape[-2], x.shape[-1])
+    ys = _lib.to_device(y, None, torch.float32, "y", cast=False).reshape(B, y.shape[-2], y.shape[-1])
+    N, C = xs.shape[1:]
     M = ys.shape[1]
     out = torch.empty((B, N, M), dtype=torch.float32, device=xs.device)
     _lib.call(xs.device, "gr_pairwise_distance_batch", xs, ys, B, N, M, C, int(bool(normalized)), out,

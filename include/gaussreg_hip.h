@@ -337,7 +337,8 @@ int gr_raster_mark_visible(int64_t P, const float* means3D, const float* h_viewm
  *
  * gr_pairwise_distance       geotransformer/modules/ops/pairwise_distance.py:4-31 (channel-last, 2-D):
  *                            out (n,m) = clamp((|x|^2 - 2 x y^T) + |y|^2, 0), or clamp(2 - 2 x y^T, 0) if
- *                            `normalized`; x y^T on fp32 MFMA.
+ *                            `normalized`; x y^T on fp32 MFMA.  The clamp keeps NaN, as torch's does: a NaN in
+ *                            row i of x (row j of y) makes row i (column j) of `out` NaN and nothing else.
  * gr_superpoint_matching     geotransformer/modules/geotransformer/superpoint_matching.py:13-50 (forward):
  *                            masks (uint8, may be null = all true), L2-normalised features (nr,c)/(ns,c);
  *                            out_* have room for num_correspondences entries; *h_num_out =
@@ -629,6 +630,15 @@ size_t gr_fps_workspace_bytes(int64_t n, int64_t batch);
 int gr_fps(const float* points, const int64_t* h_lengths, const int64_t* h_num_samples,
            const int64_t* h_start_indices, int64_t n, int64_t batch, int64_t* out_indices, void* ws,
            size_t ws_bytes, void* stream);
+/* gr_point_to_node_partition: rules the reference leaves to torch, fixed here.  (1) A point belongs to the FIRST node at its
+ * minimum distance (strict <, ascending node index, like torch.min): a node repeated at a higher index owns nothing -- mask
+ * 0, a row of padding.  (2) A node's members are listed by ascending (distance, point index): members at bit-equal distances
+ * appear in ascending index (torch.topk leaves their order open).  (3) clamp(min=0) keeps NaN, as torch's does.  A point with
+ * a NaN coordinate has no distance that compares below any other: it is assigned to node 0 (torch.min returns index 0 for a
+ * NaN column), sets node_masks[0], and is NEVER listed -- not even when node 0 has fewer than point_limit members; the
+ * reference's topk ranks it behind the 1e12 of every non-member, so it does not list it either.  The same holds for any
+ * member whose distance is not finite.  point_limit in [1, 1024]; n >= point_limit ("need at least point_limit points": torch.topk
+ * would fail too); m = 0 returns at once. */
 size_t gr_point_to_node_workspace_bytes(int64_t n, int64_t m);
 int gr_point_to_node_partition(const float* points, int64_t n, const float* nodes, int64_t m, int point_limit,
                                int64_t* point_to_node, uint8_t* node_masks, int64_t* node_knn_indices,

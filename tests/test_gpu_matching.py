@@ -140,12 +140,17 @@ def test_point_to_node_demo_shape_vs_oracle():
     part = np.partition(full, 1, axis=0)
     clear = (part[1] - part[0]) > 1e-5
     assert clear.mean() > 0.99 and np.array_equal(p2n[clear], wp[clear])
-    if np.array_equal(p2n, wp):
-        assert np.array_equal(nm, wm) and np.array_equal(km, wkm)
-        same_rows = (idx == widx).all(1)
-        assert same_rows.mean() > 0.98  # rows differ only where two member distances tie within fp noise
-        for r in np.nonzero(~same_rows)[0]:
-            assert set(idx[r]) == set(widx[r])
+    # masks and rows of every node none of whose possible members is unclear: an unclear point may belong to either of its two
+    # nearest nodes (`full` holds the oracle's own distances)
+    two = np.argpartition(full, 1, axis=0)[:2]
+    sure = np.ones(Mn, bool)
+    sure[two[:, ~clear].reshape(-1)] = False
+    assert sure.mean() > 0.9
+    assert np.array_equal(nm[sure], wm[sure]) and np.array_equal(km[sure], wkm[sure])
+    same_rows = (idx == widx).all(1)
+    assert same_rows[sure].mean() > 0.98  # rows differ only where two member distances tie within fp noise
+    for r in np.nonzero(~same_rows & sure)[0]:
+        assert set(idx[r]) == set(widx[r])
 
 
 def test_local_global_registration_vs_reference_golden():
