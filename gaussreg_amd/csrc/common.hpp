@@ -209,10 +209,11 @@ int depth_sort_views(const uint32_t* field, const uint32_t* rect_raw, uint64_t* 
                      hipStream_t stream, const int2* key_mm = nullptr, int nb_mm = 0, int32_t* overflow_flag = nullptr,
                      int overflow_value = 0, const DepthSortTotals* chunk_totals = nullptr,
                      const DepthSortSegments* segments = nullptr);
-// key_mm != null: the four-launch path for a few views per call (top-digit pass + in-LDS bucket sort): key_mm = [V][nb_mm]
-// {smallest, largest} non-zero field of a block of Gaussians (0x7fffffff / 0 for a block without one); a bucket that does
-// not fit stores overflow_value into *overflow_flag (a negative value; a positive one is OR-ed in) and the order is then NOT
-// valid -- repeat with key_mm = null.
+// key_mm != null: the bucket path (top-digit pass + in-LDS bucket sort): key_mm = [V][nb_mm] {smallest, largest} non-zero
+// field of a block of Gaussians -- with more than four views of a WAVE of the preprocess, reduced by a launch of the sort --
+// (0x7fffffff / 0 for one without any); a bucket that does not fit stores overflow_value into *overflow_flag (a negative
+// value; a positive one is OR-ed in) and the order is then NOT valid -- repeat with key_mm = null.  chunk_totals->chunk is
+// a power of two of at least 2 048.
 bool depth_sort_msd_possible(int64_t P, int V, int key_bits);
 
 // kpconv.hip: the forward's row-flag and gather launches (WF (m, K*Cin) and max(neighbor_num, 1) per query), reused by the

@@ -26,8 +26,9 @@
 //     stay in that XCD's L2.
 // Per pass: count (per-chunk digit histogram) -> scan (prefix over the chunks of a view, digit bases) -> scatter.
 //
-// Few views per call (one camera: the launch chain IS the frame time, nine launches of 5-9 us): ONE such pass on the TOP
-// bits, then one launch that finishes every bucket inside LDS ("MSD" below, four launches).  The top digit is taken
+// Bucket path ("MSD" below; few views per call -- one camera: the launch chain IS the frame time, nine launches of 5-9 us --
+// and many, see further down): ONE such pass on the TOP bits, then one launch that finishes every bucket inside LDS (four
+// launches).  The top digit is taken
 // relative to the view's own key range -- bucket = (key - kmin) >> s with s = bits(kmax - kmin) - 9, from the per-block
 // minima / maxima the preprocess kernel leaves -- so the 512 buckets cover exactly the depths that occur; what is left of
 // a key is s <= 18 bits.  A bucket (a contiguous run of <= MSD_CAP words, already in id order) becomes 32-bit items
@@ -36,6 +37,20 @@
 // A bucket above MSD_CAP raises a flag: the caller repeats the frame with the three-pass sort.
 // The same launch can add up the tile instances of every chunk of sorted positions (DepthSortTotals: what the binning needs
 // first, so that no count launch follows the sort).
+//
+// Many views per call (more than four: the traffic is the cost, not the launches) take the same path in another shape --
+// one trip of the words through memory instead of three, one count and one scan launch instead of three, and no
+// chunk_total_kernel in the binning (the bucket launch adds the chunk totals up):
+//   * key ranges: the preprocess (preprocess_many_kernel) leaves a {min, max} pair per WAVE, without a barrier in its view
+//     loop; ds_range_kernel, one workgroup per view, reduces a view's row to {kmin, s}, and the count, scatter and bucket
+//     launches read it the way they read a caller's range;
+//   * buckets in two size classes: 256 threads and MANY_CAP items for the usual ones (four workgroups per CU), which list
+//     the few larger ones for a fixed grid of the 512-thread / MSD_CAP instance; from eight views on all buckets of a
+//     view sit on one XCD, like its chunks in the passes before;
+//   * a workgroup's life is a handful of dependent trips to memory: the bucket's size, shift and start come in one, and
+//     the words are loaded and gathered four per thread at a time; the chunk totals are summed per thread and reduced once
+//     per bucket.
+// Sizes from tools/depth_buckets_model.py (profiles/r11_depth_buckets_model.txt); measurements in DESIGN.md section 3.3.
 //
 // A second user, grid_subsample.hip (DepthSortSegments): ragged segments (clouds) instead of equal strides, key range known
 // to the caller, the 26-bit payload = the voxel key, ids leaving as global point indices -- the (cloud, voxel key, index)
@@ -73,6 +88,10 @@ constexpr int MSD_T = 512;         // threads of a bucket workgroup
 constexpr int MSD_IDX_BITS = 14;
 constexpr int MSD_CAP = 7936;      // items per bucket: 2 x 31 KB of items + 16 KB of counters -> two workgroups per CU
 static_assert(MSD_CAP <= (1 << MSD_IDX_BITS), "bucket positions must fit the item's index field");
+constexpr int MSD_FEW_VIEWS = 4;   // up to here: one bucket class, key ranges per preprocess block (the launch chain counts)
+// more views: the small class.  8 KB of counters + 2 x 4032 items + the chunk totals = 40 724 bytes: four workgroups per CU
+// (512 threads and 4 096 items, three workgroups per CU, measured the same: 0.336 against 0.331 ms for the whole sort)
+constexpr int MANY_T = 256, MANY_CAP = 4032;
 
 // FIRST: the source is the raw key array (all P entries of the view, culled ones have a zero depth field)
 // MSD (with FIRST): the digit is the top of the key relative to the view's range; every block derives the range from the
@@ -149,17 +168,51 @@ __global__ __launch_bounds__(DS_T) void ds_count_kernel(int P, int V, int nchunk
   for (int d = threadIdx.x; d < DS_BINS; d += DS_T) dst[d] = (uint16_t)s_h[d];  // <= DS_CHUNK
 }
 
+// More than four views per call: the preprocess leaves a {min, max} pair per WAVE (no barrier in its view loop); one
+// workgroup per view reduces the view's row to range[v] = {kmin, s}, which the count, scatter and bucket launches then read
+// the way a caller-supplied range is read (key_mm == nullptr).
+constexpr int DS_RANGE_T = 1024;
+__global__ __launch_bounds__(DS_RANGE_T) void ds_range_kernel(const int2* __restrict__ key_mm, int nb_mm,
+                                                              uint32_t* __restrict__ range) {
+  __shared__ int s_mm[2][DS_RANGE_T / WAVE];
+  const int v = blockIdx.x;
+  const int2* row = key_mm + (int64_t)v * nb_mm;
+  int mn = 0x7fffffff, mx = 0;
+#pragma unroll 4
+  for (int i = threadIdx.x; i < nb_mm; i += DS_RANGE_T) {
+    const int2 m = row[i];
+    mn = min(mn, m.x);
+    mx = max(mx, m.y);
+  }
+  mn = wave_min_i32_dpp(mn);
+  mx = wave_max_i32_dpp(mx);
+  if ((threadIdx.x & (WAVE - 1)) == 0) s_mm[0][threadIdx.x / WAVE] = mn, s_mm[1][threadIdx.x / WAVE] = mx;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 0; w < DS_RANGE_T / WAVE; ++w) mn = min(mn, s_mm[0][w]), mx = max(mx, s_mm[1][w]);
+    if (mx == 0) mn = 0;  // nothing visible
+    const uint32_t span = (uint32_t)(mx - mn);
+    int sh = max(0, 32 - __clz((int)span) - DS_BITS);  // span < 2^(sh + 9)
+    if (span == 0u) sh = 0;
+    range[2 * v] = (uint32_t)mn;
+    range[2 * v + 1] = (uint32_t)sh;
+  }
+}
+
 // per (view, digit): exclusive prefix over the chunks.  A workgroup owns 64 digits of one view; its sixteen waves split the
 // chunk range (two sweeps over the u16 table: sums, then prefixes), lanes = adjacent digits (128-byte rows).
 constexpr int DS_SCAN_NW = 16;  // waves per scan workgroup
 __global__ __launch_bounds__(DS_SCAN_NW* WAVE) void ds_scan_kernel(int nchunk, const uint16_t* __restrict__ hist,
                                                                    uint32_t* __restrict__ offs,
                                                                    int32_t* __restrict__ digit_total,
-                                                                   int32_t* __restrict__ clear, int n_clear, int bins) {
+                                                                   int32_t* __restrict__ clear, int n_clear, int bins,
+                                                                   int32_t* __restrict__ clear_one) {
   __shared__ unsigned int s_part[DS_SCAN_NW][WAVE];
-  // (bucket path: the chunk totals the bucket launch adds into)
+  // (bucket path: the chunk totals the bucket launch adds into; clear_one: the length of the list of large buckets, where
+  // a call has both)
   if (clear != nullptr && blockIdx.x == 0)
     for (int i = threadIdx.x; i < n_clear; i += DS_SCAN_NW * WAVE) clear[i] = 0;
+  if (clear_one != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *clear_one = 0;
   const int v = blockIdx.x / (DS_BINS / WAVE), dg = blockIdx.x % (DS_BINS / WAVE);
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   const int d = dg * WAVE + lane;
@@ -392,6 +445,7 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
                                                                int32_t* __restrict__ flag, int flag_value, DepthSortTotals ct,
                                                                DepthSortSegments sg) {
   constexpr int BNW = BT / WAVE, BSTEPS = (BCAP + BT - 1) / BT, DPT = DS_BINS / BT;  // digits per thread in the scan
+  constexpr int GRP = 4;  // global loads a thread keeps in flight
   static_assert(DS_BINS % BT == 0 && BCAP <= (1 << MSD_IDX_BITS), "bucket workgroup shape");
   __shared__ unsigned int s_cnt[BNW][DS_BINS];
   __shared__ uint32_t s_item[2][BCAP];
@@ -400,16 +454,23 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
   const int lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
   auto one_bucket = [&](const int v, const int d) {
   const int32_t* trow = digit_total + v * DS_BINS;
+  // everything the workgroup has to know about its bucket in ONE trip to memory (a workgroup lives for a handful of
+  // dependent round trips and little else): its size, the view's shift and the totals of the digits below it, which say
+  // where it starts -- loaded before the size decides whether the bucket is this launch's at all
+  int below[DPT];
+#pragma unroll
+  for (int u = 0; u < DPT; ++u) below[u] = trow[min((int)threadIdx.x + u * BT, DS_BINS - 1)];
   const int n = trow[d];
+  const int sh = (int)range[2 * v + 1];
   if (n <= n_lo || n > n_hi) {  // (n_lo >= 0: empty buckets leave here)
     // two size classes: the launch of the small class lists the buckets of the large one (usually none)
     if (n > n_hi && sg.big_list != nullptr && threadIdx.x == 0) sg.big_list[atomicAdd(sg.big_cnt, 1)] = v * DS_BINS + d;
     return;
   }
-  // where the bucket starts: the totals of the digits below
   {
     int mine = 0;
-    for (int i = threadIdx.x; i < d; i += BT) mine += trow[i];
+#pragma unroll
+    for (int u = 0; u < DPT; ++u) mine += (int)threadIdx.x + u * BT < d ? below[u] : 0;
     const int ws = wave_sum_i32_dpp(mine);
     if (lane == 0) s_w[wv] = ws;
   }
@@ -417,7 +478,6 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
   int start = 0;
 #pragma unroll
   for (int w = 0; w < BNW; ++w) start += s_w[w];
-  const int sh = (int)range[2 * v + 1];
   const int64_t vbase = sg.seg_off ? (int64_t)sg.seg_off[v] : (int64_t)v * P;
   const int64_t base = vbase + start;
   const int32_t id_add = sg.seg_off ? sg.seg_off[v] : 0;  // segments with offsets: ids leave as positions in the whole array
@@ -438,8 +498,10 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
   }
   // one entry leaves: id, rectangle, and its tile instances into the total of the chunk its position falls into.  64
   // consecutive positions touch at most two chunks: two wave sums, then one LDS add each.
-  const int chunk0 = ct.chunk_total != nullptr ? start / ct.chunk : 0;
-  const bool few_chunks = ct.chunk_total != nullptr && (start + n - 1) / ct.chunk - chunk0 < (int)(sizeof(s_ct) / sizeof(int));
+  // (ct.chunk is a power of two of at least 2 048, depth_sort_views checks it: positions -> chunks by a shift)
+  const int csh = 31 - __clz(ct.chunk);
+  const int chunk0 = ct.chunk_total != nullptr ? start >> csh : 0;
+  const bool few_chunks = ct.chunk_total != nullptr && ((start + n - 1) >> csh) - chunk0 < (int)(sizeof(s_ct) / sizeof(int));
   if (ct.chunk_total != nullptr && few_chunks)
     for (int i = threadIdx.x; i < (int)(sizeof(s_ct) / sizeof(int)); i += BT) s_ct[i] = 0;
   auto emit = [&](int j, bool have, uint64_t k) {  // wave-uniform call; j = position in the bucket
@@ -454,7 +516,7 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
       int x0, y0, w = 0, h = 0;
       if (have && r != 0u) rect_decode(r, (int)id, vbase, ct.rec, ct.gx, ct.gy, x0, y0, w, h);
       const int nt = have ? w * h : 0;
-      const int ck = (start + j) / ct.chunk;
+      const int ck = (start + j) >> csh;
       const int ck_first = __builtin_amdgcn_readfirstlane(ck);
       const int a = wave_sum_i32_dpp(ck == ck_first ? nt : 0), b = wave_sum_i32_dpp(ck == ck_first ? 0 : nt);
       if (lane == 0) {
@@ -466,6 +528,38 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
           if (b) atomicAdd(&ct.chunk_total[v * ct.nchunk + ck_first + 1], b);
         }
       }
+    }
+  };
+  // the same for a bucket that went through the LDS sort (n <= BCAP: it touches at most NACC chunks): a thread adds the
+  // tile instances of its entries up per chunk in registers, and the wave sums are taken once per bucket (emit_done), not
+  // twice per 64 entries -- with the division that the shift replaced they were three quarters of this loop's instructions
+  constexpr int NACC = BCAP / 2048 + 2;
+  int acc[NACC];
+#pragma unroll
+  for (int a = 0; a < NACC; ++a) acc[a] = 0;
+  auto emit_sorted = [&](int j, bool have, uint64_t k) {
+    const uint32_t id = (uint32_t)(k >> 26) & idmask, r = (uint32_t)k & 0x3ffffffu;
+    if (have) {
+      ids_out[base + j] = (int32_t)id + id_add;
+      if (sg.gather64 != nullptr) sg.key64_out[base + j] = sg.gather64[(int64_t)id + id_add];
+      else if (sg.key64_out != nullptr) sg.key64_out[base + j] = ((uint64_t)v << sg.key64_shift) | r;
+      else rect_out[base + j] = r;
+    }
+    if (ct.chunk_total != nullptr) {
+      int x0, y0, w = 0, h = 0;
+      if (have && r != 0u) rect_decode(r, (int)id, vbase, ct.rec, ct.gx, ct.gy, x0, y0, w, h);
+      const int nt = have ? w * h : 0;
+      const int rel = ((start + j) >> csh) - chunk0;
+#pragma unroll
+      for (int a = 0; a < NACC; ++a) acc[a] += rel == a ? nt : 0;
+    }
+  };
+  auto emit_done = [&]() {  // (s_ct was cleared before the sort's barriers)
+    if (ct.chunk_total == nullptr) return;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+      const int t = wave_sum_i32_dpp(acc[a]);
+      if (lane == 0 && t != 0) atomicAdd(&s_ct[a], t);
     }
   };
   auto flush_totals = [&]() {
@@ -484,8 +578,18 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
     flush_totals();
     return;
   }
-  for (int i = threadIdx.x; i < n; i += BT)
-    s_item[0][i] = ((uint32_t)(keys[base + i] >> (id_bits + 26)) << MSD_IDX_BITS) | (uint32_t)i;
+  // (GRP loads of a thread in flight, then their LDS stores: a loop of one load per trip waits for every load before it
+  // issues the next one -- n / BT round trips in a row, and a workgroup lives for little else)
+  for (int u0 = 0; u0 * BT < n; u0 += GRP) {
+    uint64_t kw[GRP];
+#pragma unroll
+    for (int u = 0; u < GRP; ++u) kw[u] = keys[base + min((u0 + u) * BT + (int)threadIdx.x, n - 1)];
+#pragma unroll
+    for (int u = 0; u < GRP; ++u) {
+      const int i = (u0 + u) * BT + (int)threadIdx.x;
+      if (i < n) s_item[0][i] = ((uint32_t)(kw[u] >> (id_bits + 26)) << MSD_IDX_BITS) | (uint32_t)i;
+    }
+  }
   // a wave's share of the bucket: whole 64-item steps
   const int seg = ((n + BNW - 1) / BNW + WAVE - 1) / WAVE * WAVE;
   const int w0 = wv * seg, w1 = min(n, w0 + seg);
@@ -560,11 +664,20 @@ __global__ __launch_bounds__(BT) void ds_bucket_sort_kernel(int P, int n_lo, int
     cur ^= 1;
     __syncthreads();  // the bases are read to the end before the next round clears them; the items are in place
   }
-  for (int j0 = 0; j0 < n; j0 += BT) {
-    const int j = j0 + (int)threadIdx.x;
-    if (j0 + wv * WAVE >= n) break;  // wave-uniform
-    emit(j, j < n, j < n ? keys[base + (s_item[cur][j] & ((1u << MSD_IDX_BITS) - 1u))] : 0ull);
+  // the words in sorted order: GRP gathers of a thread in flight (see above), then they leave
+  for (int u0 = 0; u0 * BT < n; u0 += GRP) {
+    uint64_t kw[GRP];
+#pragma unroll
+    for (int u = 0; u < GRP; ++u)
+      kw[u] = keys[base + (s_item[cur][min((u0 + u) * BT + (int)threadIdx.x, n - 1)] & ((1u << MSD_IDX_BITS) - 1u))];
+#pragma unroll
+    for (int u = 0; u < GRP; ++u) {
+      const int j = (u0 + u) * BT + (int)threadIdx.x;
+      if ((u0 + u) * BT + wv * WAVE >= n) break;  // wave-uniform
+      emit_sorted(j, j < n, j < n ? kw[u] : 0ull);
+    }
   }
+  emit_done();
   flush_totals();
   };  // one_bucket
   if (n_lo > 0 && sg.big_list != nullptr) {
@@ -598,10 +711,11 @@ size_t depth_sort_table_bytes(int64_t P, int V) {
 }
 
 bool depth_sort_msd_possible(int64_t P, int V, int key_bits) {
-  // the word holds [<= 18 rest bits | id | 26 rectangle bits]; a few views per call only: with 32 the launches are not the
-  // cost, and two passes + the bucket launch measured no faster than three passes (0.433 vs 0.440 ms) while the preprocess
-  // paid 0.06 ms for the per-view key ranges
-  return V >= 1 && V <= 4 && P <= (1ll << 20) && key_bits <= 2 * DS_BITS + DS_BITS;
+  // the word holds [<= 18 rest bits | id | 26 rectangle bits].  Any number of views: up to four the launch chain is the
+  // cost and the path saves five launches; with more it saves two of the three trips of the words through memory, two
+  // count and two scan launches and the binning's chunk-total launch (the buckets then run in two size classes and the key
+  // ranges come from per-wave pairs, see depth_sort_views; measurements: DESIGN.md section 3.3)
+  return V >= 1 && P <= (1ll << 20) && key_bits <= 2 * DS_BITS + DS_BITS;
 }
 
 // field, rect_raw: [V*P] per (view, Gaussian), left untouched.  keys_a, keys_b: [V*P] scratch.  Out: ids_out / rect_out
@@ -636,20 +750,35 @@ int depth_sort_views(const uint32_t* field, const uint32_t* rect_raw, uint64_t* 
                "depth_sort: bucket path misused");
     const uint32_t dmask = DS_BINS - 1;
     if (segments != nullptr) range = const_cast<uint32_t*>(sg.range_in);
+    // more than four views: key_mm holds a pair per wave of the preprocess; one launch reduces every view's row, and from
+    // here on the range is read like a caller's
+    const bool many = segments == nullptr && V > MSD_FEW_VIEWS;
+    if (many) {
+      hipLaunchKernelGGL(ds_range_kernel, dim3((unsigned)V), dim3(DS_RANGE_T), 0, stream, key_mm, nb_mm, range);
+      sg.range_in = range;
+      key_mm = nullptr;
+    }
     hipLaunchKernelGGL((ds_count_kernel<true, true>), grid, blk, 0, stream, (int)P, V, nchunk, nvalid_out, field,
                        (const uint64_t*)nullptr, 0, dmask, hist, key_mm, nb_mm, range, sg);
-    DepthSortTotals ct{nullptr, 1, 0, nullptr, 0, 0};
+    DepthSortTotals ct{nullptr, 2048, 0, nullptr, 0, 0};
     if (chunk_totals != nullptr) ct = *chunk_totals;
+    GR_REQUIRE(ct.chunk >= 2048 && (ct.chunk & (ct.chunk - 1)) == 0, "depth_sort: chunk totals per %d entries (a power of two >= 2048)",
+               ct.chunk);
     // many small buckets (segments: tens of thousands of a few hundred entries): those first, on small workgroups, which
     // also list the few large ones for a launch of a fixed grid (a workgroup per bucket that only finds out that the
     // bucket is not its size cost 22 us at 32 768 buckets)
+    // many views of a scene: the same two classes at other sizes.  A view's depths spread over 330 - 410 of its 512
+    // buckets; at the headline shape (profiles/r11_depth_buckets_model.txt) 92 % of the entries sit in buckets of up to
+    // MANY_CAP and ten buckets per view are larger (none above MSD_CAP) -- the small class keeps four workgroups of four
+    // waves on a CU, the listed ones go to the 512-thread instance.
     constexpr int SMALL_T = 128, SMALL_CAP = 1024;
-    const bool two_sizes = segments != nullptr;
-    const int bins_used = (two_sizes && sg.bins_used > 0 && sg.bins_used < DS_BINS) ? sg.bins_used : DS_BINS;
-    GR_REQUIRE(!(two_sizes && chunk_totals != nullptr), "depth_sort: chunk totals and segments together");
+    const bool two_sizes = segments != nullptr || many;
+    const int bins_used = (segments != nullptr && sg.bins_used > 0 && sg.bins_used < DS_BINS) ? sg.bins_used : DS_BINS;
+    GR_REQUIRE(!(segments != nullptr && chunk_totals != nullptr), "depth_sort: chunk totals and segments together");
     if (two_sizes) sg.big_cnt = big, sg.big_list = big + 1;
     hipLaunchKernelGGL(ds_scan_kernel, dim3((unsigned)(V * (DS_BINS / WAVE))), dim3(DS_SCAN_NW * WAVE), 0, stream, nchunk, hist,
-                       offs, dbase, two_sizes ? big : ct.chunk_total, two_sizes ? 1 : V * ct.nchunk, bins_used);
+                       offs, dbase, segments != nullptr ? big : ct.chunk_total, segments != nullptr ? 1 : V * ct.nchunk, bins_used,
+                       many ? big : (int32_t*)nullptr);
     if (ordered)
       hipLaunchKernelGGL((ds_scatter_kernel<true, false, true, true>), grid, blk, 0, stream, (int)P, V, nchunk, nvalid_out, field,
                          (const uint64_t*)nullptr, 0, id_bits, dmask, offs, dbase, keys_a, rect_raw, rect_out, ids_out, nvalid_out,
@@ -659,14 +788,21 @@ int depth_sort_views(const uint32_t* field, const uint32_t* rect_raw, uint64_t* 
                          (const uint64_t*)nullptr, 0, id_bits, dmask, offs, dbase, keys_a, rect_raw, rect_out, ids_out, nvalid_out,
                          range, sg);
     dim3 bgrid((unsigned)bins_used, (unsigned)V);
-    if (two_sizes && V >= 32) {
+    if (two_sizes && V >= (many ? 8 : 32)) {  // (views: as the count and scatter launches above, ds_block)
       sg.bins_used = bins_used;
       sg.xcd_segments = V;
       bgrid = dim3((unsigned)(bins_used * ((V + 7) / 8 * 8)), 1);
     }
-    const int split = two_sizes ? SMALL_CAP : 0;
+    const int split = many ? MANY_CAP : two_sizes ? SMALL_CAP : 0;
     const dim3 biggrid = two_sizes ? dim3(std::min<unsigned>(1024u, (unsigned)V * DS_BINS), 1) : bgrid;
-    if (two_sizes) {
+    if (many) {
+      if (ordered)
+        hipLaunchKernelGGL((ds_bucket_sort_kernel<true, MANY_T, MANY_CAP>), bgrid, dim3(MANY_T), 0, stream, (int)P, 0, split, dbase,
+                           range, keys_a, id_bits, ids_out, rect_out, overflow_flag, overflow_value, ct, sg);
+      else
+        hipLaunchKernelGGL((ds_bucket_sort_kernel<false, MANY_T, MANY_CAP>), bgrid, dim3(MANY_T), 0, stream, (int)P, 0, split, dbase,
+                           range, keys_a, id_bits, ids_out, rect_out, overflow_flag, overflow_value, ct, sg);
+    } else if (two_sizes) {
       if (ordered)
         hipLaunchKernelGGL((ds_bucket_sort_kernel<true, SMALL_T, SMALL_CAP>), bgrid, dim3(SMALL_T), 0, stream, (int)P, 0, split, dbase,
                            range, keys_a, id_bits, ids_out, rect_out, overflow_flag, overflow_value, ct, sg);
@@ -702,7 +838,7 @@ int depth_sort_views(const uint32_t* field, const uint32_t* rect_raw, uint64_t* 
       hipLaunchKernelGGL((ds_count_kernel<false, false>), grid, blk, 0, stream, (int)P, V, nchunk, nvalid_out, field, kin,
                          word_shift, dmask, hist, (const int2*)nullptr, 0, (uint32_t*)nullptr, sg);
     hipLaunchKernelGGL(ds_scan_kernel, dim3((unsigned)(V * (DS_BINS / WAVE))), dim3(DS_SCAN_NW * WAVE), 0, stream, nchunk, hist,
-                       offs, dbase, (int32_t*)nullptr, 0, DS_BINS);
+                       offs, dbase, (int32_t*)nullptr, 0, DS_BINS, (int32_t*)nullptr);
 #define GR_DS_SCATTER(F, L, O)                                                                                            \
   hipLaunchKernelGGL((ds_scatter_kernel<F, L, O>), grid, blk, 0, stream, (int)P, V, nchunk, nvalid_out, field, kin, \
                      word_shift, id_bits, dmask, offs, dbase, kout, rect_raw, rect_out, ids_out, first ? nvalid_out : nullptr, \

@@ -171,7 +171,8 @@ struct Geom {
   int32_t* chunk_max;    // [1] largest chunk total
   void* ds_table;        // depth-sort histograms / offsets
   size_t ds_table_bytes;
-  int2* key_mm;          // [V][ceil(P / 256)] smallest / largest depth field of a preprocess block (a few views per call only)
+  int2* key_mm;          // [V][ceil(P / 256)] smallest / largest depth field of a preprocess block (up to four views per call),
+                         // [V][4 ceil(P / 256)] of a preprocess wave (more views)
   int32_t* nvis;         // [V] visible (depth-ordered) Gaussians per view
   int32_t* totals;       // [V] instances per view, [V] largest chunk total of every view, [1] depth-overflow flag, [3] pad --
   DevView* views;        // -- immediately followed by the [MAX_VIEWS] camera table: ONE upload clears the flag and sets the cameras
@@ -200,7 +201,8 @@ Geom carve_geom(void* p, int64_t P, int V, int64_t tiles) {
   g.chunk_max = c.take<int32_t>(1);
   g.ds_table_bytes = depth_sort_table_bytes(P, V);
   g.ds_table = c.take<char>(g.ds_table_bytes);
-  g.key_mm = c.take<int2>((V <= 4 ? V : 0) * ((P + 255) / 256));  // (depth_sort_msd_possible)
+  // (depth_sort_msd_possible; more than four views: a pair per wave of the preprocess, not per block)
+  g.key_mm = c.take<int2>(V <= 4 ? V * ((P + 255) / 256) : P <= (1ll << 20) ? V * ((P + 255) / 256) * (256 / WAVE) : 0);
   g.nvis = c.take<int32_t>(V);
   g.totals = c.take<int32_t>(2 * V + 4 + MAX_VIEWS * (sizeof(DevView) / sizeof(int32_t)));
   g.views = reinterpret_cast<DevView*>(g.totals ? g.totals + 2 * V + 4 : nullptr);

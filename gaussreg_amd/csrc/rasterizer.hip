@@ -53,6 +53,8 @@ constexpr int SH_ROW = 13;  // float4 per staged Gaussian: 12 used + 1 pad -> co
 // Gaussians that survive the culling of THE view (12 float4 loads per visible lane, straight into registers) -- with a
 // single camera 40 % of the benchmark scene never reads its SH; with several views every Gaussian is visible somewhere,
 // and the coalesced stream through LDS below is the better way.
+// The body (preprocess_body.hpp) is included in preprocess_kernel (WAVE_MM = false: the kernel as it was) and in
+// preprocess_many_kernel (more than four views per call with the bucket depth sort behind it: per-wave key ranges).
 template <bool HAS_SH, bool HAS_COV, bool SH16, bool LATE>
 __global__ __launch_bounds__(256) void preprocess_kernel(
     int P, int D, int M, int V, const DevView* __restrict__ views, const float* __restrict__ means3D,
@@ -62,230 +64,26 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ dfield,
     uint32_t* __restrict__ rect_raw, int32_t* __restrict__ far_flag, DevView cam1, int far_seq,
     int2* __restrict__ key_mm) {
-  // LATE (one camera per call): the camera arrives in the kernel arguments `cam1` (no upload in front of the frame); the first
-  // block leaves it in `views` for the kernels behind this one.  far_seq: the value a far depth stores into *far_flag
-  // (a per-call stamp when nobody cleared the flag, else 1).
-  if (LATE && blockIdx.x == 0 && threadIdx.x < (int)(sizeof(DevView) / 4))
-    reinterpret_cast<float*>(const_cast<DevView*>(views))[threadIdx.x] = reinterpret_cast<const float*>(&cam1)[threadIdx.x];
-  __shared__ float4 s_sh[(SH16 && !LATE) ? WAVE * SH_ROW : 1];
-  __shared__ float4 s_rec[256 / WAVE][4 * REC_PLANE];
-  __shared__ int s_mm[2][2][256 / WAVE];  // [view parity][min, max][wave]
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  float shr[SH16 ? 48 : 1];
-  if (SH16 && !LATE) {
-    // degree-3 SH = 192 B per Gaussian: the block's 48 KB are read as a coalesced float4 stream and transposed through
-    // LDS (row stride 13 float4 keeps the per-thread ds_read_b128 conflict-free), one wave's 64 Gaussians at a time through
-    // the same 13 KB -- a 52 KB staging area for all four waves capped the CU at 12 resident waves for the whole view loop.
-    const int g0 = blockIdx.x * 256;
-    const int n_here = min(256, P - g0);
-    const float4* src = reinterpret_cast<const float4*>(shs + (int64_t)g0 * 48);
-#pragma unroll 1
-    for (int w = 0; w < 256 / WAVE; ++w) {
-      const int lim = min(WAVE, n_here - w * WAVE) * 12;
-#pragma unroll
-      for (int u = 0; u < 3; ++u) {
-        const int f = threadIdx.x + u * 256;
-        if (f < lim) {
-          const int g = f / 12, j = f - g * 12;
-          s_sh[g * SH_ROW + j] = src[w * WAVE * 12 + f];
-        }
-      }
-      __syncthreads();
-      if ((int)threadIdx.x / WAVE == w && i < P) {
-#pragma unroll
-        for (int j = 0; j < 12; ++j) {
-          const float4 t = s_sh[(threadIdx.x & (WAVE - 1)) * SH_ROW + j];
-          shr[4 * j] = t.x;
-          shr[4 * j + 1] = t.y;
-          shr[4 * j + 2] = t.z;
-          shr[4 * j + 3] = t.w;
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // Threads past the end stay alive (they help to write their wave's records below) on a clamped index and store nothing.
-  const bool valid = i < P;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave_first = i - lane;  // first Gaussian of this wave
-  i = min(i, P - 1);
-  const float p[3] = {means3D[3 * (int64_t)i], means3D[3 * (int64_t)i + 1], means3D[3 * (int64_t)i + 2]};
-  const float opacity = opacities[i];
-  float c6[6];
-  if (HAS_COV) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) c6[k] = cov3D_precomp[6 * (int64_t)i + k];
-  }
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  const float* sh = HAS_SH ? shs + (int64_t)i * M * 3 : nullptr;
-  float cpre[3] = {0.f, 0.f, 0.f};
-  if (!HAS_SH) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) cpre[k] = colors_precomp[3 * (int64_t)i + k];
-  }
-  float4* wrec = s_rec[threadIdx.x / WAVE];
-  float mod_prev = 0.f;
-  bool have_cov = HAS_COV;
-  for (int v = 0; v < V; ++v) {
-    const DevView& cam = LATE ? cam1 : views[v];
-    const int64_t o = (int64_t)v * P + i;
-    int out_radius = 0;
-    uint32_t out_field = 0u, out_rect = 0u;  // culled: depth field 0
-    float out_depth = 0.f, out_sxx = INFINITY, out_syy = INFINITY, out_kc = 0.f;
-    float2 out_xy = make_float2(0.f, 0.f);
-    float4 out_co = make_float4(0.f, 0.f, 0.f, 0.f);
-    bool shade = false;
-    float rgb[3] = {0.f, 0.f, 0.f};
-    float pv[3];
-    xform4x3(cam.view, p, pv);
-    if (pv[2] > 0.2f) {
-      float ph[4];
-      xform4x4(cam.proj, p, ph);
-      const float pw = 1.0f / (ph[3] + 0.0000001f);
-      const float pprojx = ph[0] * pw, pprojy = ph[1] * pw;
-      if (!HAS_COV && (!have_cov || cam.scale_mod != mod_prev)) {
-        // scales / rotations are read again here rather than held across the view loop: cov3D changes only with scale_mod
-        float sc[3], rot[4];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) sc[k] = scales[3 * (int64_t)i + k];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) rot[k] = rotations[4 * (int64_t)i + k];
-        cov3d_from_scale_rot(sc, cam.scale_mod, rot, c6);
-        have_cov = true;
-        mod_prev = cam.scale_mod;
-      }
-      float cv[3];
-      cov2d(pv, cam.fx, cam.fy, cam.tanx, cam.tany, c6, cam.view, cv);
-      const float det = cv[0] * cv[2] - cv[1] * cv[1];
-      if (det != 0.0f) {
-        const float det_inv = 1.f / det;
-        const float mid = 0.5f * (cv[0] + cv[2]);
-        const float sq = sqrtf(fmaxf(0.1f, mid * mid - det));
-        const float l1 = mid + sq, l2 = mid - sq;
-        const float my_radius = ceilf(3.f * sqrtf(fmaxf(l1, l2)));
-        const float px = ((pprojx + 1.0f) * (float)W - 1.0f) * 0.5f;
-        const float py = ((pprojy + 1.0f) * (float)H - 1.0f) * 0.5f;
-        int rmin[2], rmax[2];
-        get_rect(px, py, (int)my_radius, gx, gy, rmin, rmax);
-        const int ntile = (rmax[0] - rmin[0]) * (rmax[1] - rmin[1]);
-        if (ntile != 0) {
-          shade = true;
-          if (HAS_SH && SH16 && LATE) {
-            // one camera: the coefficients are loaded here and used at once -- ahead of this view's stores, which a load
-            // issued after them would wait for
-            const float4* s4 = reinterpret_cast<const float4*>(shs + (int64_t)i * 48);
-#pragma unroll
-            for (int jj = 0; jj < 12; ++jj) {
-              const float4 t4 = s4[jj];
-              shr[4 * jj] = t4.x;
-              shr[4 * jj + 1] = t4.y;
-              shr[4 * jj + 2] = t4.z;
-              shr[4 * jj + 3] = t4.w;
-            }
-            sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return shr[k * 3 + c]; }, rgb);
-          }
-          out_depth = pv[2];
-          out_radius = (int)my_radius;
-          out_xy = make_float2(px, py);
-          out_co = make_float4(cv[2] * det_inv, -cv[1] * det_inv, cv[0] * det_inv, opacity);
-          // kc: k such that |d|^2 > |pc| * k  ==>  fp32 power < pc for any cutoff pc < 0 (blend
-          // cell culling).  power <= -|d|^2 (0.5/l1 - 2e-6): the 2e-6 covers the fp32 evaluation
-          // error of the quadratic form given lambda_min(cov) >= 0.3 (the +0.3 dilation).
-          const bool cullable = det > 0.0f && l2 >= 0.29f && l1 < 1.0e4f;
-          const float kc = cullable ? 1.001f / (0.5f / l1 - 2.0e-6f) : INFINITY;
-          out_kc = kc;
-          // Tile rectangle actually emitted: the reference square (radius = ceil(3 sigma_max)) intersected with the
-          // bounding box of the region where alpha can reach 1/255.  A pixel contributes only if fp32 power >= pc
-          // (pc as in the blend, with margin); inside the cutoff circle rc2 the fp32 quadratic form is within
-          // 2e-6 rc2 of the exact one, whose level set {0.5 d^T A d <= c'} has half-extents sqrt(2 c' Sigma_xx / yy).
-          // Only (tile, Gaussian) pairs that blend nothing are dropped, so the image is unchanged; `radii` is not.
-          if (cullable) {
-            // blend cell culling along the axes: |dx|^2 > c' * sxx (or |dy|^2 > c' * syy) ==> no contribution
-            out_sxx = 2.0f * cv[0] * 1.004f;
-            out_syy = 2.0f * cv[2] * 1.004f;
-            const float pcm = __logf(255.0f * opacity) + 2.0e-3f;
-            if (pcm > 0.0f) {
-              const float cp = pcm + 2.0e-6f * (pcm * kc);
-              const float hx = sqrtf(2.0f * cp * cv[0]) * 1.001f + 1.0e-2f;
-              const float hy = sqrtf(2.0f * cp * cv[2]) * 1.001f + 1.0e-2f;
-              // pixels x with |x - px| <= hx: [ceil(px - hx), floor(px + hx)] -> tiles
-              const float xlo = ceilf(px - hx), xhi = floorf(px + hx), ylo = ceilf(py - hy), yhi = floorf(py + hy);
-              if (xlo > -1.0e6f && xhi < 1.0e6f && ylo > -1.0e6f && yhi < 1.0e6f) {
-                rmin[0] = max(rmin[0], (int)floorf(xlo / (float)TILE));
-                rmin[1] = max(rmin[1], (int)floorf(ylo / (float)TILE));
-                rmax[0] = min(rmax[0], (int)floorf(xhi / (float)TILE) + 1);
-                rmax[1] = min(rmax[1], (int)floorf(yhi / (float)TILE) + 1);
-                if (rmax[0] < rmin[0]) rmax[0] = rmin[0];
-                if (rmax[1] < rmin[1]) rmax[1] = rmin[1];
-              }
-            }
-          }
-          uint32_t dk = __float_as_uint(out_depth) - KEY_DEPTH_BASE;  // out_depth > 0.2 > 0.125
-          if (dk >= (1u << KEY_DEPTH_BITS)) {
-            dk = (1u << KEY_DEPTH_BITS) - 1;
-            if (LATE) *far_flag = far_seq; else atomicOr(far_flag, 1);
-          }
-          out_field = dk;
-          out_rect = pack_rect(rmin, rmax);
-        }
-      }
-    }
-    if (valid) {
-      __builtin_nontemporal_store(out_radius, radii + o);  // (an output nobody in the pipeline reads)
-      dfield[o] = out_field;
-      rect_raw[o] = out_rect;
-    }
-    // Record pieces 0, 1 and 3 go to LDS before the colour is evaluated: the SH coefficients are the largest live set of
-    // the loop, and no other record value is held in registers beside them.
-    wrec[0 * REC_PLANE + lane] = make_float4(out_xy.x, out_xy.y, out_sxx, out_syy);
-    wrec[1 * REC_PLANE + lane] = out_co;
-    wrec[3 * REC_PLANE + lane] = make_float4(__int_as_float(out_radius), out_depth, 0.f, 0.f);  // wide-rectangle fallback only
-    if (key_mm != nullptr) {  // the block's key range of this view, for the bucket sort (depth_sort.hip)
-      const uint32_t fld = valid ? out_field : 0u;
-      const int mn = wave_min_i32_dpp(fld != 0u ? (int)fld : 0x7fffffff), mx = wave_max_i32_dpp((int)fld);
-      if (lane == 0) s_mm[v & 1][0][threadIdx.x / WAVE] = mn, s_mm[v & 1][1][threadIdx.x / WAVE] = mx;
-      __syncthreads();  // (one barrier per view: the other half of s_mm is the one the next view writes)
-      if (threadIdx.x == 0) {
-        int bmn = 0x7fffffff, bmx = 0;
-#pragma unroll
-        for (int w = 0; w < 256 / WAVE; ++w) bmn = min(bmn, s_mm[v & 1][0][w]), bmx = max(bmx, s_mm[v & 1][1][w]);
-        key_mm[(int64_t)v * gridDim.x + blockIdx.x] = make_int2(bmn, bmx);
-      }
-    }
-    if (shade && !(HAS_SH && SH16 && LATE)) {
-      if (HAS_SH) {
-        if (SH16) sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return shr[k * 3 + c]; }, rgb);
-        else sh_to_rgb(D, p, cam.campos, [&](int k, int c) { return sh[k * 3 + c]; }, rgb);
-      } else {
-        rgb[0] = cpre[0]; rgb[1] = cpre[1]; rgb[2] = cpre[2];
-      }
-    }
-    wrec[2 * REC_PLANE + lane] = make_float4(rgb[0], rgb[1], rgb[2], out_kc);
-    // The wave's 64 records (4 KB, contiguous) leave through LDS: lane l stores piece l % 4 of record 16 k + l / 4 in
-    // store k, so every store instruction covers whole lines.  (Each lane writing its own record piece by piece costs four
-    // partial-line writes per record: measured 0.26 ms of the 0.77 ms kernel at 32 views.)  Culled Gaussians are never
-    // gathered: their 64-B line is not touched at all.
-    const unsigned long long vis = __ballot(valid && out_radius > 0);
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    float4* wout = rec + 4 * ((int64_t)v * P + wave_first);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int rl = 16 * k + lane / 4;
-      const float4 piece = wrec[(lane & 3) * REC_PLANE + rl];
-      // streaming stores (whole 64-byte records, 1 KB per instruction): the records are next read by the blend, three
-      // stages later and in another order -- kept out of the caches they no longer evict the depth fields and rectangles the
-      // sort is about to read (32 views: preprocess 0.61 -> 0.56 ms, depth sort 0.46 -> 0.41 ms)
-      if ((vis >> rl) & 1ull) {
-        typedef float pre_f4 __attribute__((ext_vector_type(4)));
-        __builtin_nontemporal_store(pre_f4{piece.x, piece.y, piece.z, piece.w}, reinterpret_cast<pre_f4*>(wout + 4 * rl + (lane & 3)));
-      }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
+  constexpr bool WAVE_MM = false;
+#define GR_PREPROCESS_BODY_OK
+#include "preprocess_body.hpp"
+#undef GR_PREPROCESS_BODY_OK
+}
+
+template <bool HAS_SH, bool HAS_COV, bool SH16>
+__global__ __launch_bounds__(256) void preprocess_many_kernel(
+    int P, int D, int M, int V, const DevView* __restrict__ views, const float* __restrict__ means3D,
+    const float* __restrict__ shs, const float* __restrict__ colors_precomp,
+    const float* __restrict__ opacities, const float* __restrict__ scales,
+    const float* __restrict__ rotations, const float* __restrict__ cov3D_precomp, int W, int H,
+    int32_t* __restrict__ radii, float4* __restrict__ rec, uint32_t* __restrict__ dfield,
+    uint32_t* __restrict__ rect_raw, int32_t* __restrict__ far_flag, DevView cam1, int far_seq,
+    int2* __restrict__ key_mm) {
+  constexpr bool WAVE_MM = true;
+  constexpr bool LATE = false;
+#define GR_PREPROCESS_BODY_OK
+#include "preprocess_body.hpp"
+#undef GR_PREPROCESS_BODY_OK
 }
 
 // slow path of the depth sort: the field becomes the full 32 depth bits (visible depths are > 0.2: non-zero)
@@ -305,7 +103,8 @@ __global__ __launch_bounds__(256) void full_keys_kernel(int64_t n, const float4*
 // ever materialised and every global write is a full coalesced line (scattering 4-byte ids straight into per-tile lists
 // was measured first: 62 M partial-line writes per 32 views cost 1.1 ms in the L2 alone).
 //   count    a few views: a workgroup owns a chunk, histograms its tiles in LDS -> chunk_cnt, chunk_total; many views:
-//            only the chunk totals (chunk_total_kernel)
+//            only the chunk totals -- out of the bucket launch of the depth sort, or by chunk_total_kernel behind the
+//            three-pass sort
 //   scan     chunk totals -> chunk bases (per view); a few views: per chunk an exclusive scan over the tiles -> seg_off
 //            (many views: the scatter scans the tile counts it builds anyway and writes its own row of seg_off)
 //   scatter  a workgroup owns a chunk; wave w owns a quarter of its Gaussians and a private cursor per tile in LDS
@@ -1362,8 +1161,8 @@ bool verify_this_frame() {
 // depths crowd into a sliver of the key range: every frame would be ordered twice); per host thread
 thread_local int g_bucket_cooldown = 0;
 constexpr int BUCKET_COOLDOWN_FRAMES = 256;
-// One call of the waiting period.  The unit is library calls that COULD have used the bucket sort (`possible`): calls of
-// many views, which never take it, do not run the period down.
+// One call of the waiting period.  The unit is library calls that COULD have used the bucket sort (`possible`), of few views
+// or of many: a call the sort cannot serve (too many Gaussians for its id field) does not run the period down.
 bool bucket_sort_allowed(bool possible) {
   if (!possible) return false;
   if (g_bucket_cooldown == 0) return true;
@@ -1554,12 +1353,18 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
   // a deferred frame of a few views: the four-launch depth sort (a bucket that outgrows LDS raises the far word with the
   // sign flipped; the caller then takes the plain path, which always sorts in three passes)
   // (a plain call reads the counts itself: bit 1 of the far word says "overflow" there and the ordering is redone in place)
+  // more than four views per call (always a plain call): the same sort, fed by per-wave key ranges (preprocess_many_kernel)
   const bool msd_possible = depth_sort_msd_possible(P, num_views, KEY_DEPTH_BITS);
   const bool msd = msd_possible && (defer_ev != nullptr ? defer_ev->bucket_sort : bucket_sort_allowed(true));
   int2* const mm_out = msd ? g.key_mm : nullptr;
 #define GR_PRE(SH, COV, S16)                                                                       \
   if (S16 && num_views == 1)                                                                       \
     hipLaunchKernelGGL((preprocess_kernel<SH, COV, S16, S16>), grd, blk, 0, stream, (int)P, D, M, num_views, \
+                       g.views, means3D, shs, colors_precomp, opacities, scales, rotations,        \
+                       cov3D_precomp, W, H, radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * num_views, cam1, far_seq, \
+                       mm_out);                                                                    \
+  else if (msd && num_views > 4)                                                                   \
+    hipLaunchKernelGGL((preprocess_many_kernel<SH, COV, S16>), grd, blk, 0, stream, (int)P, D, M, num_views, \
                        g.views, means3D, shs, colors_precomp, opacities, scales, rotations,        \
                        cov3D_precomp, W, H, radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * num_views, cam1, far_seq, \
                        mm_out);                                                                    \
@@ -1582,6 +1387,7 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
   const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
   int32_t h_chunk_max = 0;
   auto sort_and_count = [&](int key_bits, bool buckets = true) -> int {
+    bool totals_sorted = false;
     {
       KernelTimer timer("raster_depth_sort", stream);
       // visible Gaussians of every view in depth order (ties: Gaussian id): ids -> order_b, rectangles -> rects
@@ -1589,11 +1395,14 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
       // ... and with the mailbox: no count / scan launch either, the scatter does both (its SEG_SELF_RAW variant)
       const bool self_seg = msd_now && defer_ev != nullptr && defer_ev->mail != nullptr && nchunk <= SCAN_SINGLE_ROW &&
                             num_views <= 4;
+      // many views: the bucket launch adds up the chunk totals as well -- the binning starts at its scan
+      totals_sorted = msd_now && num_views > 4;
       const DepthSortTotals ct{g.chunk_total, BIN_CHUNK, nchunk, g.rec, gx, gy};
       int rcs = depth_sort_views(g.dfield, g.rect_raw, g.keys_a, g.keys_b, g.order_b, g.rects, g.nvis, P, num_views, key_bits,
                                  g.ds_table, g.ds_table_bytes, stream, msd_now ? g.key_mm : nullptr,
-                                 (int)((P + 255) / 256), g.totals + 2 * num_views, defer_ev != nullptr ? -far_seq : 2,
-                                 self_seg ? &ct : nullptr);
+                                 num_views > 4 ? (int)((P + 255) / 256) * (256 / WAVE) : (int)((P + 255) / 256),
+                                 g.totals + 2 * num_views, defer_ev != nullptr ? -far_seq : 2,
+                                 self_seg || totals_sorted ? &ct : nullptr);
       if (rcs != GR_OK) return rcs;
       if (self_seg) {
         defer_ev->by_mail = true;
@@ -1622,8 +1431,9 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
         GR_LAUNCH_CHECK();
       } else {
         // only the chunk totals: the scatter (SEG_SELF_SCAN) counts the tiles of its chunk and writes its row of seg_off
-        hipLaunchKernelGGL(chunk_total_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T), 0, stream, (int)P,
-                           num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_total);
+        if (!totals_sorted)
+          hipLaunchKernelGGL(chunk_total_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T), 0, stream, (int)P,
+                             num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_total);
         if (!short_rows)
           hipLaunchKernelGGL(chunk_max_kernel, dim3(1), dim3(1024), 0, stream, num_views * nchunk, g.chunk_total, g.chunk_max);
         GR_LAUNCH_CHECK();
