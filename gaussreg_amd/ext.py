@@ -64,6 +64,33 @@ class SupportGrid:
         return self.ws
 
 
+def _stage(dev, q_points, s_points, q_lengths, s_lengths, radius, grid):
+    """What both searches do first: the clouds on the GPU (a self-search stays ONE tensor), the lengths on the host, the
+    workspace -- the shared one, or the grid's -- and whether the grid already holds these supports.
+    -> q, s, head (the arguments every radius entry point begins with), ws, sig, reuse, key (what the grid holds afterwards)"""
+    same = s_points is q_points or (s_points.data_ptr() == q_points.data_ptr() and s_points.shape == q_points.shape)
+    q = q_points if q_points.is_cuda else q_points.to(dev)
+    s = q if same else (s_points if s_points.is_cuda else s_points.to(dev))
+    ql, sl = q_lengths.tolist(), s_lengths.tolist()
+    nq, ns, nb = q.shape[0], s.shape[0], len(ql)
+    head = (q, s, _lib.host_i64(ql), _lib.host_i64(sl), nq, ns, nb, float(radius))
+    # (the radius entry points take their workspace in the middle of the argument list: it is passed like any tensor)
+    if grid is None:
+        return q, s, head, _lib.workspace(q.device, _lib.lib().gr_radius_workspace_bytes(nq, ns, nb)), None, 0, None
+    ws = grid.workspace(q.device, nq, ns, nb)
+    key = (s.data_ptr(), ns, nb, float(radius), tuple(sl))
+    reuse = 1 if (grid.key == key and ns > 0 and nq > 0) else 0
+    return q, s, head, ws, grid.sig, reuse, key if (ns > 0 and nq > 0 and nb > 0) else None
+
+
+def _searched(grid, key, s):
+    """After a search: the grid holds the supports `s` (key None: nothing was binned) -> `reuse` for a repeat of the call."""
+    if grid is None:
+        return 0
+    grid.key, grid._keep = key, s
+    return 1 if key is not None else 0
+
+
 def _radius(q_points, s_points, q_lengths, s_lengths, radius, neighbor_limit, grid, checks):
     dev = _lib.require_gpu()
     if checks:
@@ -76,78 +103,43 @@ def _radius(q_points, s_points, q_lengths, s_lengths, radius, neighbor_limit, gr
             _check_contig(t, n)
         if q_lengths.numel() != s_lengths.numel():
             raise RuntimeError("q_lengths and s_lengths must have the same number of batch elements")
-    out_device = q_points.device
-    same = s_points is q_points or (s_points.data_ptr() == q_points.data_ptr() and s_points.shape == q_points.shape)
-    q = q_points if q_points.is_cuda else q_points.to(dev)
-    s = q if same else (s_points if s_points.is_cuda else s_points.to(dev))
-    dev = q.device
-    ql, sl = q_lengths.tolist(), s_lengths.tolist()
-    nq, ns, nb = q.shape[0], s.shape[0], len(ql)
-    hq, hs = _lib.host_i64(ql), _lib.host_i64(sl)
+    q, s, head, ws, sig, reuse, key = _stage(dev, q_points, s_points, q_lengths, s_lengths, radius, grid)
+    dev, (nq, ns, nb) = q.device, head[4:7]
     info = (ctypes.c_int64 * 4)()
-    # (the radius entry points take their workspace in the middle of the argument list: it is passed like any tensor)
-    if grid is None:
-        ws = _lib.workspace(dev, _lib.lib().gr_radius_workspace_bytes(nq, ns, nb))
-        _lib.call(dev, "gr_radius_count", q, s, hq, hs, nq, ns, nb, float(radius), ws, ws.numel(), info)
-    else:
-        ws = grid.workspace(dev, nq, ns, nb)
-        key = (s.data_ptr(), ns, nb, float(radius), tuple(sl))
-        reuse = 1 if (grid.key == key and ns > 0 and nq > 0) else 0
-        _lib.call(dev, "gr_radius_count_cached", q, s, hq, hs, nq, ns, nb, float(radius), ws, ws.numel(), info, grid.sig,
-                  reuse)
-        grid.key = key if (ns > 0 and nq > 0 and nb > 0) else None
-        grid._keep = s
+    _lib.call(dev, "gr_radius_count_cached", *head, ws, ws.numel(), info, sig, reuse)
+    _searched(grid, key, s)
     width = int(info[0])
     if neighbor_limit is not None and neighbor_limit > 0:
         width = min(width, int(neighbor_limit))
     out = torch.empty((nq, width), dtype=torch.int64, device=dev)
     if nq > 0 and width > 0:
         _lib.call(dev, "gr_radius_fill", q, s, nq, ns, nb, float(radius), width, info, out, ws=ws)
-    return _lib.like_input(out, out_device)
+    return _lib.like_input(out, q_points.device)
 
 
-_WIDTH_HINT = {}  # (radius, neighbor_limit) -> largest neighbour count of the last search of that call site
+_WIDTH_HINT = {}  # (radius, neighbor_limit) -> largest neighbour count of the LAST search of that call site (not a running maximum)
 
 
 def _radius_limited(q_points, s_points, q_lengths, s_lengths, radius, neighbor_limit, grid, contiguous=True):
     """radius_search with neighbor_limit > 0: the (nq, limit) rows are allocated before anything is counted and ONE
     kernel searches, ranks and writes them (gr_radius_search); the read-back of max_count only decides whether the
     reference would have returned fewer columns (radius_search.py:25-26 keeps min(max_count, limit))."""
-    dev = _lib.require_gpu()
-    out_device = q_points.device
-    same = s_points is q_points or (s_points.data_ptr() == q_points.data_ptr() and s_points.shape == q_points.shape)
-    q = q_points if q_points.is_cuda else q_points.to(dev)
-    s = q if same else (s_points if s_points.is_cuda else s_points.to(dev))
-    dev = q.device
-    ql, sl = q_lengths.tolist(), s_lengths.tolist()
-    nq, ns, nb = q.shape[0], s.shape[0], len(ql)
+    q, s, head, ws, sig, reuse, key = _stage(_lib.require_gpu(), q_points, s_points, q_lengths, s_lengths, radius, grid)
+    dev, (nq, ns, nb) = q.device, head[4:7]
     limit = int(neighbor_limit)
-    hq, hs = _lib.host_i64(ql), _lib.host_i64(sl)
     info = (ctypes.c_int64 * 6)()
-    if grid is None:
-        ws = _lib.workspace(dev, _lib.lib().gr_radius_workspace_bytes(nq, ns, nb))
-        sig, reuse = None, 0
-    else:
-        ws = grid.workspace(dev, nq, ns, nb)
-        key = (s.data_ptr(), ns, nb, float(radius), tuple(sl))
-        reuse = 1 if (grid.key == key and ns > 0 and nq > 0) else 0
-        sig = grid.sig
     # Row stride of the search.  The reference's limit is an upper bound chosen by calibration and can be far above
     # what a level ever returns (the demo pyramid: limit 89, largest count 18): rows of `limit` columns would be 5 x the
     # bytes, written by the kernel and read again by the truncating copy.  A call site (radius, limit) therefore
-    # remembers the largest count it has seen and searches with rows of that width + a margin (a multiple of 8: whole
+    # remembers the largest count of its last call and searches with rows of that width + a margin (a multiple of 8: whole
     # 64-byte sectors per row piece, streaming stores); a call whose largest count does not fit is repeated at the full
     # limit -- the result is the same tensor either way.
     hint = _WIDTH_HINT.get((float(radius), limit))
     stride = limit if hint is None else min(limit, max(8, (hint + max(2, hint // 4) + 7) // 8 * 8))
     while True:
         out = torch.empty((nq, stride), dtype=torch.int64, device=dev)
-        _lib.call(dev, "gr_radius_search", q, s, hq, hs, nq, ns, nb, float(radius), stride, out, ws, ws.numel(), info,
-                  sig, reuse)
-        if grid is not None:
-            grid.key = key if (ns > 0 and nq > 0 and nb > 0) else None
-            grid._keep = s
-            reuse = 1 if grid.key is not None else 0  # (a repeat finds the supports binned)
+        _lib.call(dev, "gr_radius_search", *head, stride, out, ws, ws.numel(), info, sig, reuse)
+        reuse = _searched(grid, key, s)
         if int(info[0]) <= stride or stride == limit:
             break
         stride = limit
@@ -160,7 +152,7 @@ def _radius_limited(q_points, s_points, q_lengths, s_lengths, radius, neighbor_l
         # (contiguous=False: the column slice of the searched rows, row stride `stride` -- what the reference itself returns
         # when it truncates, radius_search.py:26; saves a copy of the whole result where nobody needs it dense)
         out = out[:, :width].contiguous() if contiguous else out[:, :width]
-    return _lib.like_input(out, out_device)
+    return _lib.like_input(out, q_points.device)
 
 
 def radius_neighbors(q_points, s_points, q_lengths, s_lengths, radius, grid=None):

@@ -91,8 +91,8 @@ int gr_radius_fill(const float* q, const float* s, int64_t nq, int64_t ns, int64
  *      32-hit network -> the same with its 64-hit network -> the 64-hit network behind a pre-selection of the `limit`
  *      nearest hits (limit <= 56: rows truncated far below the hit count, the coarsest pyramid levels) -> count + fill,
  *      stepping back one level every 256 calls;
- *   5  always try the pre-selecting kernel first (gr_radius_search only; gr_radius_count has no width to select for and
- *      takes the plain 64-hit network);
+ *   5  always try the pre-selecting kernel first; where there is no width it can select for -- limit > 56, and
+ *      gr_radius_count, which has no width at all -- the plain 64-hit network (mode 4) is tried first instead;
  *   2 / 4  always try the thread-per-query kernel first, 32- / 64-hit network (csrc/radius_tq.hpp: one wave = 64
  *      cell-ordered queries, candidates through the vector L1, hits sorted in registers, rows through LDS); queries beyond
  *      the network are finished exactly by their wave; a query with more than 192 hits hands the call back to count + fill;

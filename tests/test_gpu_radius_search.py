@@ -295,3 +295,46 @@ def test_column_slice_on_request_instead_of_a_dense_copy():
         assert dense.is_contiguous() and dense.shape == want.shape and np.array_equal(dense.cpu().numpy(), want)
         assert sliced.shape == want.shape and not sliced.is_contiguous() and sliced.stride(1) == 1
         assert torch.equal(sliced, dense)
+
+
+_CELLS = {}  # (case) -> h_info[3] of the first mode that ran: every mode must report the same grid
+
+
+def test_h_info_contract_of_search_and_count(search_mode):
+    """What the entry points leave in h_info (include/gaussreg_hip.h), pinned per mode on a cloud whose largest count is below
+    32 -- a fresh call site of the default mode starts on the 32-hit network and finishes there -- as a self-search
+    (h_info[2] = 1) and with separate queries (0).  gr_radius_search: [0] the oracle's width, [4] = 1 unless the mode is
+    count + fill, [3] the same in every mode.  gr_radius_count: [1] = -1 where a thread-per-query kernel left tiles for
+    gr_radius_fill (modes 2 - 5), the count pass's block maximum (>= 0) in modes 0 and 1.  Rows = the oracle's."""
+    from gaussreg_amd import _lib
+    from oracle import capi
+    L = _lib.lib()
+    rng = np.random.default_rng(41)
+    s = rng.random((3000, 3)).astype(np.float32)
+    q = rng.random((1000, 3)).astype(np.float32)
+    sl, ql = np.array([3000], np.int64), np.array([1000], np.int64)
+    radius, limit = 0.0917, 40
+    ts, tq = _t(s), _t(q)
+    for case, pts, t, lens, same in (("self", s, ts, sl, 1), ("queries", q, tq, ql, 0)):
+        want = capi.radius_neighbors(pts, s, lens, sl, radius)
+        nq, width = want.shape
+        assert 0 < width < 32
+        info, out = _info(t, ts, lens.tolist(), sl.tolist(), radius, limit)
+        print(case, "mode", search_mode, "search h_info", info)
+        assert info[0] == width and info[2] == same and info[3] > 0
+        assert info[4] == (0 if search_mode == 0 else 1)
+        assert _CELLS.setdefault(case, info[3]) == info[3]
+        assert np.array_equal(out[:, :width].cpu().numpy(), want) and bool((out[:, width:] == 3000).all())
+        # the bare search: count, then fill at the width the count reports
+        cinfo = (ctypes.c_int64 * 4)()
+        ws = torch.empty(L.gr_radius_workspace_bytes(nq, 3000, 1), dtype=torch.uint8, device=t.device)
+        head = (_lib.ptr(t), _lib.ptr(ts), _lib.host_i64(lens.tolist()), _lib.host_i64(sl.tolist()), nq, 3000, 1)
+        _lib.check(L.gr_radius_count(*head, float(radius), _lib.ptr(ws), ws.numel(), cinfo, _lib.stream_ptr(t.device)))
+        print(case, "mode", search_mode, "count h_info", list(cinfo))
+        assert cinfo[0] == width and cinfo[2] == same and cinfo[3] == info[3]
+        assert (cinfo[1] == -1) if search_mode >= 2 else (cinfo[1] >= 0)
+        rows = torch.empty((nq, width), dtype=torch.int64, device=t.device)
+        _lib.check(L.gr_radius_fill(_lib.ptr(t), _lib.ptr(ts), nq, 3000, 1, float(radius), width, cinfo, _lib.ptr(rows),
+                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(t.device)))
+        torch.cuda.synchronize()
+        assert np.array_equal(rows.cpu().numpy(), want)
