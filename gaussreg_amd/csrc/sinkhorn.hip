@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "common.hpp"
+#include "../../include/gaussreg_hip_train_matching.h"
 
 namespace gr {
 namespace {
@@ -554,6 +555,424 @@ __global__ __launch_bounds__(WAVE) void sinkhorn_small_kernel(const float* __res
   }
 }
 
+// ---------------------------------------------------------------- backward: d out / d (scores, alpha), one launch
+// (include/gaussreg_hip_train_matching.h).  With Z the padded matrix, u^0 = v^0 = 0,
+//   u^t = log_mu - LSE_j(Z + v^{t-1}),  v^t = log_nu - LSE_i(Z + u^t)  (t = 1..T),  out = Z + u^T + v^T - norm,
+// and G = d L / d out (0 on masked rows / columns), the reverse sweep is
+//   gZ = G; gu_i = sum_j G_ij; gv_j = sum_i G_ij
+//   t = T..1:  Q_ij = exp(Z_ij + u^t_i + v^t_j - log_nu_j)       gZ_ij -= gv_j Q_ij;  gu_i -= sum_j gv_j Q_ij
+//              P_ij = exp(Z_ij + u^t_i + v^{t-1}_j - log_mu_i)   gZ_ij -= gu_i P_ij;  gv_j = -sum_i gu_i P_ij;  gu = 0
+// Q and P are the column / row softmax of step t: never above 1, so this log-domain form needs no range guard.
+// One 512-thread workgroup per matrix in the forward's lane layout.  A lane keeps its row slice of Z, its row slice of gZ and
+// its column slice of Z in registers for the whole sweep (the side rows / columns beyond SK_MAIN: a wave each, as in the
+// forward); LDS holds only the per-step vectors, the column-indexed ones grouped by part so that a lane reads its 36 as nine
+// float4.  The workgroup first repeats the forward iterations (accurate expf / logf: the gradient is compared with float64)
+// and writes every u^t, v^t to its history slot in the workspace -- a slot per WORKGROUP, reused for every matrix the
+// workgroup walks -- then sweeps back, staging u^{t-1} and v^{t-2} into spare LDS buffers one step ahead of their use.
+// Masked rows and columns are taken out by selection (their staged u, v are -inf: every exponential on them is exactly 0),
+// never by multiplying grad_out: a NaN there reaches nothing.  No float atomics; every sum has a fixed order.
+constexpr int SKB_GRID = 512;                                     // workgroups = history slots, at most
+constexpr int SKB_NSIDE = (SK_MAXD + WAVE - 1) / WAVE;            // elements per lane of a side row / column
+constexpr int SKB_WAVES = SK_T / WAVE;
+constexpr int SKB_SIDES = (SK_MAXD - SK_MAIN + SKB_WAVES - 1) / SKB_WAVES;  // side rows (and side columns) per wave
+constexpr int SKB_VECS = 18;                                      // LDS vectors of SK_MAXD floats (below)
+
+// floats of one history slot: u^1..u^T (R each), v^1..v^T (C each)
+__host__ __device__ inline size_t skb_slot_floats(int R, int C, int T) { return ((size_t)T * (R + C) + 63) / 64 * 64; }
+// where column j sits in a column-indexed LDS vector: grouped by part, so lane (idx, part) reads j = part + 4 t contiguously
+__device__ __forceinline__ int skb_cp(int j) { return (j & 3) * SK_PER + (j >> 2); }
+// grad_out of one matrix; drop: (M, N), the dustbin entries have no upstream gradient
+// `take`: the entry is live; otherwise 0 (selected, so that whatever grad_out holds on a masked entry reaches nothing)
+__device__ __forceinline__ float skb_g(const float* __restrict__ g, int i, int j, int M, int N, int drop, bool take) {
+  take = take && (!drop || (i < M && j < N));
+  const float x = g[take ? (drop ? i * N + j : i * (N + 1) + j) : 0];
+  return take ? x : 0.f;
+}
+__device__ __forceinline__ float skb_quad_sum(float s) {
+  s += quad_xor1(s);
+  s += quad_xor2(s);
+  return s;
+}
+// logsumexp of the four lanes of a row / column from each lane's (max, sum exp(x - max)), accurate functions
+__device__ __forceinline__ float skb_lse_merge4(float mx, float s) {
+  float m = fmaxf(mx, quad_xor1(mx));
+  m = fmaxf(m, quad_xor2(m));
+  const float t = mx > -INFINITY ? s * expf(mx - m) : 0.f;
+  return logf(skb_quad_sum(t)) + m;
+}
+template <typename ZF>  // zf(t): element t of the slice, -inf past its end
+__device__ __forceinline__ float skb_lse36(ZF zf, const float* __restrict__ add, int stride) {
+  float x[SK_PER];
+  float m4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+  for (int t = 0; t < SK_PER; ++t) {
+    x[t] = zf(t) + add[t * stride];
+    m4[t & 3] = fmaxf(m4[t & 3], x[t]);
+  }
+  const float mx = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+  float s4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int t = 0; t < SK_PER; ++t) s4[t & 3] += expf(x[t] - mx);  // (a slice without any element: NaN, dropped by the merge)
+  return skb_lse_merge4(mx, (s4[0] + s4[1]) + (s4[2] + s4[3]));
+}
+// the same by a whole wave over z[m] + add[lane + 64 m]  (lane + 64 m < len)
+template <typename ZF>
+__device__ __forceinline__ float skb_wave_lse(ZF zf, const float* __restrict__ add, int len, int lane) {
+  float x[SKB_NSIDE];
+  float mx = -INFINITY;
+#pragma unroll
+  for (int m = 0; m < SKB_NSIDE; ++m) {
+    const int k = lane + m * WAVE;
+    x[m] = k < len ? zf(m) + add[min(k, SK_MAXD - 1)] : -INFINITY;
+    mx = fmaxf(mx, x[m]);
+  }
+  mx = wave_max_f32_dpp(mx);
+  float s = 0.f;
+#pragma unroll
+  for (int m = 0; m < SKB_NSIDE; ++m) s += lane + m * WAVE < len ? expf(x[m] - mx) : 0.f;
+  return logf(wave_sum_f32_dpp(s)) + mx;
+}
+
+__device__ __forceinline__ void sinkhorn_backward_matrix(const int b, const float* __restrict__ scores, int M, int N,
+                                                         const uint8_t* __restrict__ row_masks,
+                                                         const uint8_t* __restrict__ col_masks,
+                                                         const float* __restrict__ alpha_p, int T, float inf, int drop,
+                                                         const float* __restrict__ grad_out, float* __restrict__ grad_scores,
+                                                         float* __restrict__ grad_alpha, float* __restrict__ hist) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int R = M + 1, C = N + 1;
+  const int ld = sinkhorn_ld(C);
+  // (opaque to the optimiser: otherwise the per-element addresses and masks of the setup below, which depend on the thread
+  // alone, are hoisted out of the kernel's loop over matrices and kept alive -- in scratch -- across the whole sweep)
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));
+  float* Z = reinterpret_cast<float*>(smem);                    // the padded matrix, SK_MAXD rows (-inf past R); at the end, gZ
+  float* vec = Z + (size_t)SK_MAXD * ld;                        // SKB_VECS vectors of SK_MAXD floats, 16-byte aligned (ld % 4 == 0)
+  float* lmu = vec;                                             // natural order: indexed by row
+  float* lnu = vec + SK_MAXD;                                   //                by column
+  float* uF = vec + 2 * SK_MAXD;                                // the forward's running u, v (natural order)
+  float* vF = vec + 3 * SK_MAXD;
+  float* ur = vec + 4 * SK_MAXD;                                // [2] u^t              (-inf on masked rows), buffer t & 1
+  float* um = vec + 6 * SK_MAXD;                                // [2] u^t - log_mu
+  float* vq = vec + 8 * SK_MAXD;                                // [3] v^t - log_nu     (-inf on masked columns), buffer t % 3, by part
+  float* vr = vec + 11 * SK_MAXD;                               // [3] v^t
+  float* gu = vec + 14 * SK_MAXD;                               // natural order
+  float* gv = vec + 15 * SK_MAXD;                               // by part
+  float* rl = vec + 16 * SK_MAXD;                               // 1 / 0: row / column takes part (natural order)
+  float* cl = vec + 17 * SK_MAXD;
+  float* red = vec + SKB_VECS * SK_MAXD;                        // [16]
+  int* cnt = reinterpret_cast<int*>(red + 16);                  // [4]
+  float* hu = hist;                                             // u^t at hu[(t - 1) R + i], v^t at hv[(t - 1) C + j]
+  float* hv = hist + (size_t)T * R;
+  const float alpha = alpha_p[0];
+  const uint8_t* rm = row_masks ? row_masks + (int64_t)b * M : nullptr;
+  const uint8_t* cm = col_masks ? col_masks + (int64_t)b * N : nullptr;
+  const float* G = grad_out + (int64_t)b * (drop ? (int64_t)M * N : (int64_t)R * C);
+  if (tid < 4) cnt[tid] = 0;
+  for (int i = tid; i < SK_MAXD; i += SK_T) {
+    rl[i] = (i < R && (i >= M || !rm || rm[i])) ? 1.f : 0.f;
+    cl[i] = (i < C && (i >= N || !cm || cm[i])) ? 1.f : 0.f;
+    gu[i] = 0.f;
+    gv[i] = 0.f;
+    uF[i] = 0.f;
+    vF[i] = 0.f;
+  }
+  __syncthreads();
+  // the forward's setup: valid counts, padded scores, log_mu, log_nu, norm (learnable_sinkhorn.py:44-62)
+  int nr = 0, nc = 0;
+  for (int i = tid; i < M; i += SK_T) nr += rl[i] != 0.f ? 1 : 0;
+  for (int j = tid; j < N; j += SK_T) nc += cl[j] != 0.f ? 1 : 0;
+  if (nr) atomicAdd(&cnt[0], nr);
+  if (nc) atomicAdd(&cnt[1], nc);
+  for (int e = tid; e < R * C; e += SK_T) {
+    const int i = e / C, j = e % C;
+    const float x = (i < M && j < N) ? scores[((int64_t)b * M + i) * N + j] : alpha;
+    Z[i * ld + j] = (rl[i] != 0.f && cl[j] != 0.f) ? x : -inf;
+  }
+  // rows past the matrix: -inf, so that a column slice of 36 rows needs no length (every use adds finite values or -inf)
+  for (int e = tid; e < (SK_MAXD - R) * C; e += SK_T) Z[(R + e / C) * ld + e % C] = -INFINITY;
+  __syncthreads();
+  const float nvr = (float)cnt[0], nvc = (float)cnt[1];
+  const float norm = -logf(nvr + nvc);
+  for (int i = tid; i < SK_MAXD; i += SK_T) {
+    float x = i < M ? norm : logf(nvc) + norm;
+    if (i < R && rl[i] == 0.f) x = -inf;
+    lmu[i] = i < R ? x : 0.f;
+    float y = i < N ? norm : logf(nvr) + norm;
+    if (i < C && cl[i] == 0.f) y = -inf;
+    lnu[i] = i < C ? y : 0.f;
+  }
+  const int idx = tid / SK_PARTS, part = tid % SK_PARTS;
+  const int lane = tid & (WAVE - 1), wv = tid / WAVE;
+  const int row_len = idx < R ? (C - part + SK_PARTS - 1) / SK_PARTS : 0;
+  const int i0 = part * SK_PER;
+  const int col_len = idx < C ? max(0, min(R, i0 + SK_PER) - i0) : 0;
+  const bool row_on = idx < R && rl[idx] != 0.f, col_on = idx < C && cl[idx] != 0.f;
+  // register slices: Z and gZ (= G on the live entries) by row; the side rows of this wave
+  float zr[SK_PER], gz[SK_PER];
+  float zs[SKB_SIDES][SKB_NSIDE], gs[SKB_SIDES][SKB_NSIDE];
+  // the column slice is read from LDS at every use (stride ld: conflict-free, see sinkhorn_matrix)
+  const float* zcol = Z + (size_t)i0 * ld + min(idx, C - 1);
+  auto zc = [&](int t) { return zcol[t * ld]; };
+  float gu0 = 0.f, gu0s[SKB_SIDES];
+  {
+    const int ir = min(idx, R - 1), jc = min(idx, C - 1);
+    float s4[4] = {0.f, 0.f, 0.f, 0.f}, c4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < SK_PER; ++t) {
+      const int j = min(part + SK_PARTS * t, C - 1), i = min(i0 + t, R - 1);
+      zr[t] = t < row_len ? Z[ir * ld + j] : -INFINITY;
+      const float g = skb_g(G, ir, j, M, N, drop, t < row_len && row_on && cl[j] != 0.f);
+      const float h = skb_g(G, i, jc, M, N, drop, t < col_len && col_on && rl[i] != 0.f);
+      gz[t] = g;
+      s4[t & 3] += g;
+      c4[t & 3] += h;
+    }
+    gu0 = skb_quad_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
+    const float cs = skb_quad_sum((c4[0] + c4[1]) + (c4[2] + c4[3]));
+    if (part == 0 && col_on) gv[skb_cp(idx)] = cs;
+#pragma unroll
+    for (int k = 0; k < SKB_SIDES; ++k) {
+      const int r = SK_MAIN + wv + SKB_WAVES * k;  // side row r and side column r of this wave
+      const int rr = min(r, R - 1), rc = min(r, C - 1);
+      const bool r_on = r < R && rl[rr] != 0.f, c_on = r < C && cl[rc] != 0.f;
+      float sr = 0.f, sc = 0.f;
+#pragma unroll
+      for (int m = 0; m < SKB_NSIDE; ++m) {
+        const int q = lane + m * WAVE, j = min(q, C - 1), i = min(q, R - 1);
+        zs[k][m] = (r < R && q < C) ? Z[rr * ld + j] : -INFINITY;
+        const float g = skb_g(G, rr, j, M, N, drop, r_on && q < C && cl[j] != 0.f);
+        const float h = skb_g(G, i, rc, M, N, drop, c_on && q < R && rl[i] != 0.f);
+        gs[k][m] = g;
+        sr += g;
+        sc += h;
+      }
+      gu0s[k] = wave_sum_f32_dpp(sr);
+      sc = wave_sum_f32_dpp(sc);
+      if (lane == 0 && c_on) gv[skb_cp(rc)] = sc;
+    }
+  }
+  __syncthreads();
+  // ---- the forward iterations again, every u^t, v^t to the history slot (masked rows / columns keep 0)
+  for (int it = 0; it < T; ++it) {
+    {
+      const float lse = skb_lse36([&](int t) { return zr[t]; }, vF + part, SK_PARTS);
+      if (part == 0 && idx < R) {
+        const float x = row_on ? lmu[idx] - lse : 0.f;
+        uF[idx] = x;
+        hu[(size_t)it * R + idx] = x;
+      }
+#pragma unroll
+      for (int k = 0; k < SKB_SIDES; ++k) {
+        const int r = SK_MAIN + wv + SKB_WAVES * k;
+        if (r < R) {
+          const float l2 = skb_wave_lse([&](int m) { return zs[k][m]; }, vF, C, lane);
+          if (lane == 0) {
+            const float x = rl[r] != 0.f ? lmu[r] - l2 : 0.f;
+            uF[r] = x;
+            hu[(size_t)it * R + r] = x;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    {
+      const float lse = skb_lse36(zc, uF + i0, 1);
+      if (part == 0 && idx < C) {
+        const float x = col_on ? lnu[idx] - lse : 0.f;
+        vF[idx] = x;
+        hv[(size_t)it * C + idx] = x;
+      }
+#pragma unroll
+      for (int k = 0; k < SKB_SIDES; ++k) {
+        const int c = SK_MAIN + wv + SKB_WAVES * k;
+        if (c < C) {
+          const float l2 = skb_wave_lse([&](int m) { return Z[min(lane + m * WAVE, R - 1) * ld + c]; }, uF, R, lane);
+          if (lane == 0) {
+            const float x = cl[c] != 0.f ? lnu[c] - l2 : 0.f;
+            vF[c] = x;
+            hv[(size_t)it * C + c] = x;
+          }
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // ---- the reverse sweep.  Staging: threads [0, 144) own a row of the u buffers, threads [256, 400) a column of the v's
+  const int sj = tid - SK_T / 2;
+  const bool su_on = tid < SK_MAXD && tid < R && rl[min(tid, SK_MAXD - 1)] != 0.f;
+  const bool sv_on = sj >= 0 && sj < C && cl[min(max(sj, 0), SK_MAXD - 1)] != 0.f;
+  if (T > 0) {
+    if (tid < SK_MAXD) {
+      const float x = su_on ? uF[tid] : -INFINITY;
+      ur[(T & 1) * SK_MAXD + tid] = x;
+      um[(T & 1) * SK_MAXD + tid] = x - lmu[tid];
+    }
+    if (sj >= 0 && sj < SK_MAXD) {
+      const float x = sv_on ? vF[sj] : -INFINITY;
+      const float y = sv_on ? (T >= 2 ? hv[(size_t)(T - 2) * C + sj] : 0.f) : -INFINITY;
+      vr[(T % 3) * SK_MAXD + skb_cp(sj)] = x;
+      vq[(T % 3) * SK_MAXD + skb_cp(sj)] = x - lnu[sj];
+      vr[((T - 1) % 3) * SK_MAXD + skb_cp(sj)] = y;
+      vq[((T - 1) % 3) * SK_MAXD + skb_cp(sj)] = y - lnu[sj];
+    }
+  }
+  __syncthreads();
+  for (int t = T; t >= 1; --t) {
+    const float* urt = ur + (t & 1) * SK_MAXD;
+    const float* umt = um + (t & 1) * SK_MAXD;
+    const float* vqt = vq + (t % 3) * SK_MAXD;
+    const float* vrp = vr + ((t - 1) % 3) * SK_MAXD;
+    // next step's vectors: u^{t-1}, v^{t-2} (loaded now, stored to the spare buffers behind the barrier)
+    float pu = 0.f, pv = 0.f;
+    if (su_on && t >= 2) pu = hu[(size_t)(t - 2) * R + tid];
+    if (sv_on && t >= 3) pv = hv[(size_t)(t - 3) * C + sj];
+    {  // rows: the column softmax Q takes gv, the row softmax P takes gu
+      const float ui = urt[idx], wi = umt[idx];  // (idx < SK_MAIN <= SK_MAXD; -inf where the row takes no part)
+      const float4* q4 = reinterpret_cast<const float4*>(vqt + part * SK_PER);
+      const float4* g4 = reinterpret_cast<const float4*>(gv + part * SK_PER);
+      const float4* r4 = reinterpret_cast<const float4*>(vrp + part * SK_PER);
+      float s4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t4 = 0; t4 < SK_PER / 4; ++t4) {
+        const float4 q = q4[t4], g = g4[t4];
+        const float qq[4] = {q.x, q.y, q.z, q.w}, gg[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float x = gg[k] * expf((zr[4 * t4 + k] + ui) + qq[k]);
+          gz[4 * t4 + k] -= x;
+          s4[k] += x;
+        }
+      }
+      const float gui = (t == T ? gu0 : 0.f) - skb_quad_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
+#pragma unroll
+      for (int t4 = 0; t4 < SK_PER / 4; ++t4) {
+        const float4 r = r4[t4];
+        const float rr[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) gz[4 * t4 + k] -= gui * expf((zr[4 * t4 + k] + wi) + rr[k]);
+      }
+      if (part == 0 && idx < R) gu[idx] = row_on ? gui : 0.f;
+#pragma unroll
+      for (int k = 0; k < SKB_SIDES; ++k) {
+        const int r = SK_MAIN + wv + SKB_WAVES * k;
+        if (r < R) {
+          const float us = urt[r], ws = umt[r];
+          float x[SKB_NSIDE], s = 0.f;
+#pragma unroll
+          for (int m = 0; m < SKB_NSIDE; ++m) {
+            const int p = skb_cp(min(lane + m * WAVE, SK_MAXD - 1));
+            x[m] = lane + m * WAVE < C ? gv[p] * expf((zs[k][m] + us) + vqt[p]) : 0.f;
+            s += x[m];
+          }
+          const float gus = (t == T ? gu0s[k] : 0.f) - wave_sum_f32_dpp(s);
+#pragma unroll
+          for (int m = 0; m < SKB_NSIDE; ++m) {
+            const int p = skb_cp(min(lane + m * WAVE, SK_MAXD - 1));
+            const float y = lane + m * WAVE < C ? gus * expf((zs[k][m] + ws) + vrp[p]) : 0.f;
+            gs[k][m] -= x[m] + y;
+          }
+          if (lane == 0) gu[r] = rl[r] != 0.f ? gus : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+    {  // columns: gv_j = -sum_i gu_i P_ij
+      const float vj = vrp[skb_cp(idx)];
+      const float4* w4 = reinterpret_cast<const float4*>(umt + i0);
+      const float4* g4 = reinterpret_cast<const float4*>(gu + i0);
+      float s4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int t4 = 0; t4 < SK_PER / 4; ++t4) {
+        const float4 w = w4[t4], g = g4[t4];
+        const float ww[4] = {w.x, w.y, w.z, w.w}, gg[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) s4[k] += gg[k] * expf((zc(4 * t4 + k) + ww[k]) + vj);
+      }
+      const float s = skb_quad_sum((s4[0] + s4[1]) + (s4[2] + s4[3]));
+      if (part == 0 && idx < C) gv[skb_cp(idx)] = col_on ? -s : 0.f;
+#pragma unroll
+      for (int k = 0; k < SKB_SIDES; ++k) {
+        const int c = SK_MAIN + wv + SKB_WAVES * k;
+        if (c < C) {
+          const float vc = vrp[skb_cp(c)];
+          float a = 0.f;
+#pragma unroll
+          for (int m = 0; m < SKB_NSIDE; ++m) {
+            const int i = min(lane + m * WAVE, SK_MAXD - 1);
+            a += lane + m * WAVE < R ? gu[i] * expf((Z[min(i, R - 1) * ld + c] + umt[i]) + vc) : 0.f;
+          }
+          a = wave_sum_f32_dpp(a);
+          if (lane == 0) gv[skb_cp(c)] = cl[c] != 0.f ? -a : 0.f;
+        }
+      }
+      if (t >= 2) {
+        if (tid < SK_MAXD) {
+          const float x = su_on ? pu : -INFINITY;
+          ur[((t - 1) & 1) * SK_MAXD + tid] = x;
+          um[((t - 1) & 1) * SK_MAXD + tid] = x - lmu[tid];
+        }
+        if (sj >= 0 && sj < SK_MAXD) {
+          const float x = sv_on ? pv : -INFINITY;  // (v^0 = 0)
+          vr[((t + 1) % 3) * SK_MAXD + skb_cp(sj)] = x;
+          vq[((t + 1) % 3) * SK_MAXD + skb_cp(sj)] = x - lnu[sj];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // ---- gZ through LDS: grad_scores in row-major order, exact zeros on masked rows / columns; the dustbin sum for alpha
+#pragma unroll
+  for (int t = 0; t < SK_PER; ++t)
+    if (t < row_len) Z[idx * ld + part + SK_PARTS * t] = gz[t];
+#pragma unroll
+  for (int k = 0; k < SKB_SIDES; ++k) {
+    const int r = SK_MAIN + wv + SKB_WAVES * k;
+#pragma unroll
+    for (int m = 0; m < SKB_NSIDE; ++m)
+      if (r < R && lane + m * WAVE < C) Z[r * ld + lane + m * WAVE] = gs[k][m];
+  }
+  __syncthreads();
+  for (int e = tid; e < M * N; e += SK_T) {
+    const int i = e / N, j = e % N;
+    grad_scores[(int64_t)b * M * N + e] = (rl[i] != 0.f && cl[j] != 0.f) ? Z[i * ld + j] : 0.f;
+  }
+  float a = 0.f;
+  for (int e = tid; e < R + C - 1; e += SK_T) {  // (M, 0..N), then (0..M-1, N)
+    const int i = e < C ? M : e - C, j = e < C ? e : N;
+    a += (rl[i] != 0.f && cl[j] != 0.f) ? Z[i * ld + j] : 0.f;
+  }
+  a = wave_sum_f32_dpp(a);
+  if (lane == 0) red[wv] = a;
+  __syncthreads();
+  if (tid == 0) {
+    float s = 0.f;
+    for (int w = 0; w < SKB_WAVES; ++w) s += red[w];
+    grad_alpha[b] = s;
+  }
+}
+
+__global__ __launch_bounds__(SK_T) void sinkhorn_backward_kernel(const float* __restrict__ scores, int M, int N,
+                                                                 const uint8_t* __restrict__ row_masks,
+                                                                 const uint8_t* __restrict__ col_masks,
+                                                                 const float* __restrict__ alpha_p, int T, float inf, int drop,
+                                                                 const float* __restrict__ grad_out,
+                                                                 float* __restrict__ grad_scores, float* __restrict__ grad_alpha,
+                                                                 float* __restrict__ hist, int batch) {
+  float* slot = hist + (size_t)blockIdx.x * skb_slot_floats(M + 1, N + 1, T);
+  for (int b = blockIdx.x; b < batch; b += gridDim.x) {
+    sinkhorn_backward_matrix(b, scores, M, N, row_masks, col_masks, alpha_p, T, inf, drop, grad_out, grad_scores, grad_alpha,
+                             slot);
+    __syncthreads();  // the next matrix reuses the LDS image and the history slot
+  }
+}
+
+size_t sinkhorn_backward_lds(int M, int N) {
+  const int R = M + 1, C = N + 1, ld = sinkhorn_ld(C);
+  (void)R;
+  return sizeof(float) * ((size_t)SK_MAXD * ld + SKB_VECS * SK_MAXD + 16 + 4);
+}
+
 size_t sinkhorn_lds(int M, int N) {
   const int R = M + 1, C = N + 1, ld = sinkhorn_ld(C);
   return sizeof(float) * ((size_t)R * ld + 2 * R + 2 * C + 4 * SK_MAXD) + 96;
@@ -606,6 +1025,43 @@ extern "C" int gr_sinkhorn(const float* scores, int64_t batch, int64_t m, int64_
   }
   hipLaunchKernelGGL(sinkhorn_kernel, dim3((unsigned)batch), dim3(SK_T), lds, stream, scores, (int)m, (int)n, row_masks,
                      col_masks, alpha_dev, num_iterations, inf, out, scaling_form, (const int32_t*)nullptr, (int)batch, drop_dustbin ? 1 : 0);
+  GR_LAUNCH_CHECK();
+  return GR_OK;
+}
+
+extern "C" size_t gr_sinkhorn_backward_workspace_bytes(int64_t batch, int64_t m, int64_t n, int num_iterations) {
+  if (batch < 0 || m < 1 || n < 1 || num_iterations < 0 || std::max(m, n) + 1 > SK_MAXD) return 0;
+  return sizeof(float) * (size_t)std::min<int64_t>(batch, SKB_GRID) * skb_slot_floats((int)m + 1, (int)n + 1, num_iterations) + 256;
+}
+
+extern "C" int gr_sinkhorn_backward(const float* scores, int64_t batch, int64_t m, int64_t n, const uint8_t* row_masks,
+                                    const uint8_t* col_masks, const float* alpha_dev, int num_iterations, float inf,
+                                    int drop_dustbin, const float* grad_out, float* grad_scores, float* grad_alpha_per_matrix,
+                                    void* ws, size_t ws_bytes, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  GR_REQUIRE(batch >= 0 && batch < (int64_t)1 << 31 && m >= 1 && n >= 1 && num_iterations >= 0, "sinkhorn_backward: bad sizes");
+  GR_REQUIRE(std::max(m, n) + 1 <= SK_MAXD, "sinkhorn_backward: matrices larger than %d are not supported", SK_MAXD - 1);
+  if (batch == 0) return GR_OK;
+  GR_REQUIRE(scores && alpha_dev && grad_out && grad_scores && grad_alpha_per_matrix, "sinkhorn_backward: null argument");
+  const size_t need = gr_sinkhorn_backward_workspace_bytes(batch, m, n, num_iterations);
+  if (!ws || ws_bytes < need) {
+    set_error("sinkhorn_backward: workspace too small (%zu < %zu bytes)", ws_bytes, need);
+    return GR_ERR_WORKSPACE;
+  }
+  const size_t lds = sinkhorn_backward_lds((int)m, (int)n);
+  if (lds > 160 * 1024) {
+    set_error("sinkhorn_backward: a (%lld+1) x (%lld+1) matrix does not fit in LDS (%zu bytes)", (long long)m, (long long)n, lds);
+    return GR_ERR_UNSUPPORTED;
+  }
+  if (lds > 64 * 1024)
+    GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&sinkhorn_backward_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  KernelTimer timer("sinkhorn_backward", stream);
+  // the history slots start 256-byte aligned inside the caller's buffer
+  float* hist = reinterpret_cast<float*>(align_up(reinterpret_cast<size_t>(ws), 256));
+  hipLaunchKernelGGL(sinkhorn_backward_kernel, dim3((unsigned)std::min<int64_t>(batch, SKB_GRID)), dim3(SK_T), lds, stream, scores,
+                     (int)m, (int)n, row_masks, col_masks, alpha_dev, num_iterations, inf, drop_dustbin ? 1 : 0, grad_out,
+                     grad_scores, grad_alpha_per_matrix, hist, (int)batch);
   GR_LAUNCH_CHECK();
   return GR_OK;
 }
