@@ -14,3 +14,14 @@ def differentiable(chunk_rows=0):
     differentiable (gaussreg_amd.kpconv.differentiable; imported on use so that `import gaussreg_amd` stays light)."""
     from .kpconv import differentiable as ctx
     return ctx(chunk_rows)
+
+
+_LOSSES = ("WeightedCircleLoss", "CoarseMatchingLoss", "FineMatchingLoss", "OverallLoss", "Evaluator")
+
+
+def __getattr__(name):
+    """The training losses and metrics (gaussreg_amd.loss), imported on first use like `differentiable`."""
+    if name in _LOSSES:
+        from . import loss
+        return getattr(loss, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

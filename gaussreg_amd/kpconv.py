@@ -51,7 +51,9 @@ def differentiable(chunk_rows=0):
     """Inside this context, with grad mode on, `KPConv.forward`, `maxpool` and `nearest_upsample` run the same forward
     kernels as outside it and return tensors with a `grad_fn` whenever `s_feats` / `weights` / `bias` (or `x`) require
     grad; `KPConvFPN.forward` no longer switches grad off.  The transformer stack consults the same switch
-    (gaussreg_amd.transformer, .rpe_attention, .embedding): backbone and transformer become differentiable together.
+    (gaussreg_amd.transformer, .rpe_attention, .embedding), and so do log-Sinkhorn (gaussreg_amd.sinkhorn), the dim-0
+    `ops.index_select` of a float32 tensor that requires grad, and `model.GeoTransformer.forward`, whose training branch runs
+    only in here: backbone, transformer, patch gather and fine matching become differentiable together.
     Points, kernel points and indices get no gradient: a `q_points` / `s_points` that requires grad raises ValueError.
     Outside the context every call is inference, as before.  Thread-local.  `chunk_rows` > 0 overrides the number of
     queries the KPConv backward processes per chunk (tests)."""

@@ -5,6 +5,10 @@
                          (compute_correspondence_matrix is also what LocalGlobalRegistration uses,
                           local_global_registration.py:49-83)
 
+    SuperPointTargetGenerator   geotransformer/modules/geotransformer/superpoint_target.py:6-46
+    get_node_correspondences    geotransformer/modules/registration/matching.py:231-315 (training: the ground-truth
+                                superpoint correspondences, one fused HIP call -- csrc/node_correspondences.hip)
+
 Same constructor arguments, same forward signatures and return tuples; no parameters or buffers
 (no state-dict keys), like the reference.
 """
@@ -224,3 +228,79 @@ class LocalGlobalRegistration(nn.Module):
             _lib.call(dev, "gr_lgr_register_seg", o_rp, o_sp, o_sc, n, P, pm_ws, d_poff, B, float(self.acceptance_radius),
                       int(self.correspondence_threshold), int(self.num_refinement_steps), transforms, rows, ws=ws2)
         return o_rp, o_sp, o_sc, transforms, rows
+
+
+@torch.no_grad()
+def get_node_correspondences(ref_nodes, src_nodes, ref_knn_points, src_knn_points, transform, pos_radius, ref_masks=None,
+                             src_masks=None, ref_knn_masks=None, src_knn_masks=None, return_dense=False):
+    """registration/matching.py:231-315 -> (corr_indices (C, 2) int64, corr_overlaps (C,) float32): the pairs of patches
+    that share at least one point pair closer than `pos_radius` under `transform`, in row-major (ref, src) order, with
+    overlap = (matched ref points / valid ref points + matched src points / valid src points) / 2.
+    One call of gr_node_correspondences: no (B, K, K) tensor, the transform stays on the device, one host read-back (C).
+    The distance is evaluated as differences, then squares (the reference expands x^2 - 2xy + y^2, whose fp32 error at room
+    scale is a visible fraction of pos_radius^2); the threshold is the reference's: float(pos_radius) ** 2 rounded once to
+    float32, which is what torch.lt(fp32 tensor, python scalar) compares against.
+    `return_dense=True` (extension) also returns the dense (M, N) overlap matrix (0 where a pair does not overlap): what
+    CoarseMatchingLoss scatters the list into."""
+    dev = _lib.require_gpu()
+    out_device = ref_nodes.device
+    rn = _lib.to_device(ref_nodes, dev, **_F32)
+    dev = rn.device
+    sn = _lib.to_device(src_nodes, dev, **_F32)
+    rp, sp = _lib.to_device(ref_knn_points, dev, **_F32), _lib.to_device(src_knn_points, dev, **_F32)
+    T = _lib.to_device(transform, dev, torch.float32)
+    M, N = rn.shape[0], sn.shape[0]
+    K = rp.shape[1]
+    if tuple(rp.shape) != (M, K, 3) or tuple(sp.shape) != (N, K, 3) or tuple(T.shape) != (4, 4):
+        raise ValueError("get_node_correspondences: expected knn points of shape (M, K, 3) / (N, K, 3) and a (4, 4) transform")
+    masks = [None if m is None else _lib.to_device_bool(m, dev) for m in (ref_masks, src_masks, ref_knn_masks, src_knn_masks)]
+    for m, shape in zip(masks, ((M,), (N,), (M, K), (N, K))):
+        if m is not None and tuple(m.shape) != shape:
+            raise ValueError("get_node_correspondences: a mask of shape %s was expected, got %s" % (shape, tuple(m.shape)))
+    cap = M * N
+    idx = torch.empty((cap, 2), dtype=torch.int64, device=dev)
+    ov = torch.empty((cap,), dtype=torch.float32, device=dev)
+    count = torch.empty((1,), dtype=torch.int64, device=dev)
+    dense = torch.empty((M, N), dtype=torch.float32, device=dev) if return_dense else None
+    r2 = ctypes.c_float(float(pos_radius) ** 2).value
+    _lib.call(dev, "gr_node_correspondences", rn, sn, rp, sp, M, N, K, T, r2, *masks, idx, ov, cap, count, dense,
+              ws=_lib.lib().gr_node_correspondences_workspace_bytes(M, N, K))
+    c = int(count.item())
+    res = (idx[:c].clone(), ov[:c].clone())       # (clones: the views would keep the M * N buffers alive)
+    if return_dense:
+        res += (dense,)
+    return _lib.like_input(res, out_device)
+
+
+class SuperPointTargetGenerator(nn.Module):
+    """superpoint_target.py:6-46: at most `num_targets` of the ground-truth correspondences whose overlap exceeds
+    `overlap_threshold`, drawn without replacement; when none exceeds it, the ones of the largest overlap.  No parameters.
+    The reference draws from numpy's global RNG; `generator=` (a numpy Generator or RandomState, or an int seed) makes the
+    draw reproducible -- None keeps the reference's source.  An empty correspondence set raises ValueError (the
+    reference fails inside `.max()` of an empty tensor there)."""
+
+    def __init__(self, num_targets, overlap_threshold, generator=None):
+        super().__init__()
+        self.num_targets = num_targets
+        self.overlap_threshold = overlap_threshold
+        import numpy as np
+        self.generator = np.random.default_rng(generator) if isinstance(generator, int) else generator
+
+    @torch.no_grad()
+    def forward(self, gt_corr_indices, gt_corr_overlaps):
+        """(N, 2) int64, (N,) -> (ref indices, src indices, overlaps) of the selected correspondences."""
+        import numpy as np
+        if gt_corr_indices.shape[0] == 0:
+            raise ValueError("SuperPointTargetGenerator: no ground-truth superpoint correspondence (the two clouds do not "
+                             "overlap under the given transform)")
+        masks = torch.gt(gt_corr_overlaps, self.overlap_threshold)
+        if masks.sum() == 0:
+            masks = gt_corr_overlaps == gt_corr_overlaps.max()
+        gt_corr_overlaps, gt_corr_indices = gt_corr_overlaps[masks], gt_corr_indices[masks]
+        n = gt_corr_indices.shape[0]
+        if n > self.num_targets:
+            rng = np.random if self.generator is None else self.generator
+            sel = torch.from_numpy(np.asarray(rng.choice(np.arange(n), self.num_targets, replace=False)))
+            sel = sel.to(device=gt_corr_indices.device, dtype=torch.int64)
+            gt_corr_indices, gt_corr_overlaps = gt_corr_indices[sel], gt_corr_overlaps[sel]
+        return gt_corr_indices[:, 0], gt_corr_indices[:, 1], gt_corr_overlaps

@@ -108,17 +108,54 @@ def point_to_node_partition_batch(points, point_lengths, nodes, node_lengths, po
 _gather_flags = {}
 
 
+class _GatherRowsFunction(torch.autograd.Function):
+    """index_select along dim 0 of a float32 (n, c) matrix with a gradient: the forward is the inference path of
+    `index_select` itself, the backward gr_neighbor_pool_backward in mode 1 -- an (m,) index is an (m, 1) neighbour table, and
+    kpconv.inverted_index supplies the fixed order in which the rows that name one source row are summed (no atomics)."""
+
+    @staticmethod
+    def forward(ctx, data, index):
+        ctx.save_for_backward(data, index)
+        return index_select(data.detach(), index, 0)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        from .kpconv import inverted_index
+        data, index = ctx.saved_tensors
+        n, c = data.shape
+        m = index.shape[0]
+        go = grad_out.to(torch.float32).contiguous()
+        gx = torch.empty_like(data)
+        if n == 0 or c == 0:
+            return gx, None
+        table = index.reshape(m, 1)
+        edges, offsets = inverted_index(table, n, first_column_only=True)
+        _lib.call(data.device, "gr_neighbor_pool_backward", data, n, c, table, m, 1, 1, go, edges, offsets, gx, ws=256)
+        return gx, None
+
+
 def index_select(data, index, dim):
     """Advanced index select (modules/ops/index_select.py:4-31): `index` may have any shape; the `dim`-th dimension of
     `data` is replaced by index.shape.  The case the backbone runs (dim 0 of a 2-D fp32 feature / point tensor:
     kpconv.py:93-105, functional.py:17,63) is a HIP row gather; other dims / dtypes are reshaped onto it or, for
-    non-float data, use torch's own gather on the device."""
+    non-float data, use torch's own gather on the device.
+    Inside `gaussreg_amd.differentiable()` with grad mode on, the dim-0 case of a float32 `data` that requires grad returns a
+    tensor with a grad_fn (backward: gr_neighbor_pool_backward, mode 1); outside the context nothing changes."""
     if not isinstance(index, torch.Tensor) or index.dtype != torch.int64:
         raise RuntimeError("index must be a LongTensor")
     nd = data.dim()
     dim = dim + nd if dim < 0 else dim
     if not (0 <= dim < nd):
         raise IndexError("dim out of range")
+    if dim == 0 and data.dtype == torch.float32 and data.requires_grad:
+        from .kpconv import differentiable_active
+        if differentiable_active():
+            dev = data.device if data.is_cuda else _lib.require_gpu()
+            d = data.to(dev)                                  # (differentiable: the gradient arrives in the caller's tensor)
+            flat = d.reshape(d.shape[0], -1).contiguous()
+            out = _GatherRowsFunction.apply(flat, index.to(dev).reshape(-1).contiguous())
+            out = out.reshape(tuple(index.shape) + tuple(data.shape[1:]))
+            return out if data.is_cuda else out.to(data.device)
     if data.dtype != torch.float32:
         out = data.index_select(dim, index.reshape(-1))
     else:

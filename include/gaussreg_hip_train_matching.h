@@ -39,6 +39,34 @@ int gr_sinkhorn_backward(const float* scores, int64_t batch, int64_t m, int64_t 
                          const float* grad_out, float* grad_scores, float* grad_alpha_per_matrix, void* ws, size_t ws_bytes,
                          void* stream);
 
+/* gr_node_correspondences: the ground-truth superpoint correspondences of a training step (get_node_correspondences,
+ * geotransformer/modules/registration/matching.py:231-315) without the reference's per-pair (B, K, K) / (B, K, 3) tensors.
+ * ref_nodes (m,3), src_nodes (n,3), ref_knn_points (m,k,3), src_knn_points (n,k,3); transform_dev: the 4 x 4 row-major
+ * transform of the source, on the device; pos_radius_sq: the squared positive radius as the fp32 value the comparison
+ * uses.  ref_masks (m) / src_masks (n) / ref_knn_masks (m,k) / src_knn_masks (n,k): 1 = valid, null = all valid.
+ * A point pair matches when |p - (R q + t)|^2 < pos_radius_sq, evaluated as differences, then squares, in fp32 without
+ * FMA; only valid points of valid nodes take part.  overlap(i, j) = (ref_count / ref_valid + src_count / src_valid) / 2 in
+ * fp32 in this order, the counts being the points that have at least one partner; a pair where one side has no valid
+ * point has overlap 0.  The pairs with overlap > 0 leave in row-major (ref, src) order:
+ *   corr_indices (capacity, 2) int64, corr_overlaps (capacity): rows [0, min(C, capacity)) are written, nothing else;
+ *   count_dev: one int64 on the device, C itself -- the caller repeats with a larger buffer when C > capacity
+ *   (capacity = m * n always suffices; capacity == 0 allows null corr_* pointers);
+ *   dense_overlaps (m, n) or null: the whole overlap matrix, every element written (0 where the pair does not overlap).
+ * The enclosing-sphere test of the reference only prunes; here it is widened so that it never rejects a pair with a match.
+ * No float atomics, no atomics for ordering: two calls leave the same bits.  Three kernels and a scan (csrc/
+ * node_correspondences.hip); workspace = the transformed source patches, per-node records and the (m, n) overlap matrix:
+ *   about 4 * (m * n + 3 * n * k) + 24 * (m + n) bytes -- O(m n + n k).
+ * m, n or k == 0: GR_OK, *count_dev = 0, no kernel.  Refused before any launch: k > 256 (GR_ERR_UNSUPPORTED), m * n >= 2^31,
+ * null pointers, a workspace that is too small (GR_ERR_WORKSPACE).  gr_timing_* name: "node_correspondences". */
+/* host only; 0 for a shape the call refuses */
+size_t gr_node_correspondences_workspace_bytes(int64_t m, int64_t n, int64_t k);
+int gr_node_correspondences(const float* ref_nodes, const float* src_nodes, const float* ref_knn_points,
+                            const float* src_knn_points, int64_t m, int64_t n, int64_t k, const float* transform_dev,
+                            float pos_radius_sq, const uint8_t* ref_masks, const uint8_t* src_masks,
+                            const uint8_t* ref_knn_masks, const uint8_t* src_knn_masks, int64_t* corr_indices,
+                            float* corr_overlaps, int64_t capacity, int64_t* count_dev, float* dense_overlaps, void* ws,
+                            size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
