@@ -31,6 +31,8 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--fused-norm", action="store_true",
+                    help="run the backbone's GroupNorm layers in HIP in training too (differentiable(fused_norm=True))")
     args = ap.parse_args()
     if not args.synthetic:
         ap.error("only --synthetic is implemented: feed your own pairs through the calls shown here")
@@ -48,7 +50,7 @@ def main():
     optimizer = torch.optim.Adam(net.parameters(), lr=args.lr)
     for step in range(args.steps):
         optimizer.zero_grad(set_to_none=True)
-        with gaussreg_amd.differentiable():
+        with gaussreg_amd.differentiable(fused_norm=args.fused_norm):
             out = net(data)
             loss = criterion(out, data)
         loss["loss"].backward()

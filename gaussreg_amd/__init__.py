@@ -9,11 +9,12 @@ There is no CPU fallback: every op raises if the HIP library or a GPU is missing
 __version__ = "0.1.0"
 
 
-def differentiable(chunk_rows=0):
+def differentiable(chunk_rows=0, fused_norm=False):
     """`with gaussreg_amd.differentiable():` -- the one switch that makes the KPConv backbone and the transformer stack
-    differentiable (gaussreg_amd.kpconv.differentiable; imported on use so that `import gaussreg_amd` stays light)."""
+    differentiable (gaussreg_amd.kpconv.differentiable; imported on use so that `import gaussreg_amd` stays light).
+    `fused_norm=True`: the backbone's GroupNorm layers run in HIP in training as well."""
     from .kpconv import differentiable as ctx
-    return ctx(chunk_rows)
+    return ctx(chunk_rows, fused_norm)
 
 
 _LOSSES = ("WeightedCircleLoss", "CoarseMatchingLoss", "FineMatchingLoss", "OverallLoss", "Evaluator")

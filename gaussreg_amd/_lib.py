@@ -4,7 +4,8 @@ include/gaussreg_hip.h is the only description of the ABI: `parse_header` reads 
 into SIGNATURES, name -> (restype, argtypes), and DEFINES, the integer `#define GR_*` constants.  The training entry points
 that came after that header was closed are in include/gaussreg_hip_train.h, read the same way into TRAIN_SIGNATURES /
 TRAIN_DEFINES, and those of the matching stage in include/gaussreg_hip_train_matching.h into MATCH_TRAIN_SIGNATURES /
-MATCH_TRAIN_DEFINES; `lib()` binds the three tables.  Only the three structs
+MATCH_TRAIN_DEFINES, and those of the backbone's normalisation layers in include/gaussreg_hip_train_backbone.h into
+BACKBONE_TRAIN_SIGNATURES / BACKBONE_TRAIN_DEFINES; `lib()` binds the four tables.  Only the three structs
 that cross the boundary are mirrored by hand (they hold arrays).  A declaration the parser does not understand raises.
 
 `call` is the one way a wrapper enters the library: it turns tensors into device pointers after checking that they are
@@ -19,6 +20,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libgaussreg_hip.so")
 HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip.h")
 TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train.h")   # the training entry points added since
 MATCH_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train_matching.h")   # ... of the matching stage
+BACKBONE_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train_backbone.h")   # ... of the backbone's norms
 
 _lib = None
 
@@ -104,6 +106,8 @@ with open(TRAIN_HEADER_PATH) as _f:
     TRAIN_SIGNATURES, TRAIN_DEFINES = parse_header(_f.read())
 with open(MATCH_TRAIN_HEADER_PATH) as _f:
     MATCH_TRAIN_SIGNATURES, MATCH_TRAIN_DEFINES = parse_header(_f.read())
+with open(BACKBONE_TRAIN_HEADER_PATH) as _f:
+    BACKBONE_TRAIN_SIGNATURES, BACKBONE_TRAIN_DEFINES = parse_header(_f.read())
 
 GR_PENDING = DEFINES["GR_PENDING"]        # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
 GR_RETRY_FULL = DEFINES["GR_RETRY_FULL"]  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward
@@ -131,7 +135,7 @@ def lib():
                 "(there is no CPU fallback for the gaussreg_amd ops)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
-                                   + list(MATCH_TRAIN_SIGNATURES.items())):
+                                   + list(MATCH_TRAIN_SIGNATURES.items()) + list(BACKBONE_TRAIN_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

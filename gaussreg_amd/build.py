@@ -38,7 +38,8 @@ def build(force=False, verbose=False):
     os.makedirs(OBJDIR, exist_ok=True)
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
     headers += [os.path.join(HERE, "..", "include", h) for h in ("gaussreg_hip.h", "gaussreg_hip_train.h",
-                                                                 "gaussreg_hip_train_matching.h")]
+                                                                 "gaussreg_hip_train_matching.h",
+                                                                 "gaussreg_hip_train_backbone.h")]
     jobs = []
     objs = []
     for src in sources():

@@ -10,6 +10,7 @@
 //   gemm      out = WF (M x K*Cin) . W (K*Cin x Cout) on fp32 MFMA 32x32x2, epilogue / neighbor_num + bias
 #include <algorithm>
 
+#include "../../include/gaussreg_hip_train_backbone.h"
 #include "common.hpp"
 #include "mfma_tile.hpp"
 
@@ -744,6 +745,16 @@ __global__ __launch_bounds__(GN_T) void group_norm_stats_kernel(double* __restri
   }
 }
 
+// gr_group_norm_train: the (mean, rstd) floats that group_norm_stats_kernel left behind every segment's partials, copied to
+// stats (nseg, 2, G) for the backward pass
+__global__ __launch_bounds__(GN_T) void group_norm_stats_copy_kernel(const double* __restrict__ partial, int nblk, int groups,
+                                                                     int per_seg_doubles, int nseg, float* __restrict__ stats) {
+  const int i = blockIdx.x * GN_T + threadIdx.x;
+  if (i >= nseg * 2 * groups) return;
+  const int s = i / (2 * groups), k = i % (2 * groups);
+  stats[i] = reinterpret_cast<const float*>(partial + (int64_t)s * per_seg_doubles + (int64_t)nblk * 2 * groups)[k];
+}
+
 }  // namespace
 }  // namespace gr
 
@@ -753,7 +764,8 @@ extern "C" size_t gr_group_norm_workspace_bytes(int64_t groups) {
 
 static int group_norm_impl(const float* x, int64_t n, int64_t c, int64_t groups, const float* gamma, const float* beta,
                            float eps, float negative_slope, float* out, const int64_t* seg_off, int64_t nseg, int64_t max_seg_rows,
-                           void* ws, size_t ws_bytes, hipStream_t stream, const float* residual = nullptr) {
+                           void* ws, size_t ws_bytes, hipStream_t stream, const float* residual = nullptr,
+                           float* stats_out = nullptr) {
   GR_REQUIRE(n >= 0 && c >= 4 && groups >= 1 && groups <= gr::GN_MAXG && c % groups == 0, "group_norm: bad sizes");
   const int64_t cols4 = c / 4;
   GR_REQUIRE(c % 4 == 0 && ((cols4 <= gr::GN_T && gr::GN_T % cols4 == 0) || (cols4 > gr::GN_T && cols4 % gr::GN_T == 0)),
@@ -784,6 +796,10 @@ static int group_norm_impl(const float* x, int64_t n, int64_t c, int64_t groups,
   GR_REQUIRE(residual == nullptr || reinterpret_cast<uintptr_t>(residual) % 16 == 0, "group_norm: unaligned residual");
   hipLaunchKernelGGL(gr::group_norm_kernel<true>, dim3(nblk_b, gy), dim3(gr::GN_T), 0, stream, x, n, (int)c, (int)groups, gamma,
                      beta, eps, negative_slope, partial, nblk_a, out, seg_off, residual);
+  if (stats_out != nullptr)
+    hipLaunchKernelGGL(gr::group_norm_stats_copy_kernel, dim3((gy * 2 * (unsigned)groups + gr::GN_T - 1) / gr::GN_T),
+                       dim3(gr::GN_T), 0, stream, partial, nblk_a, (int)groups, (int)(per_seg / sizeof(double)), (int)gy,
+                       stats_out);
   GR_LAUNCH_CHECK();
   return GR_OK;
 }
@@ -818,4 +834,18 @@ extern "C" int gr_group_norm_res(const float* x, int64_t n, int64_t c, int64_t g
   GR_REQUIRE(nseg >= 0 && nseg < 65536 && max_seg_rows >= 0, "group_norm_res: bad segments");
   return group_norm_impl(x, n, c, groups, gamma, beta, eps, negative_slope, out, seg_off, nseg, max_seg_rows, ws, ws_bytes,
                          static_cast<hipStream_t>(stream_), residual);
+}
+
+// gr_group_norm_res that keeps the statistics of its apply pass for gr_group_norm_backward (group_norm_backward.hip)
+extern "C" int gr_group_norm_train(const float* x, int64_t n, int64_t c, int64_t groups, const float* gamma, const float* beta,
+                                   float eps, float negative_slope, const float* residual, float* out, float* stats,
+                                   const int64_t* seg_off, int64_t nseg, int64_t max_seg_rows, void* ws, size_t ws_bytes,
+                                   void* stream_) {
+  GR_REQUIRE(stats != nullptr || n == 0, "group_norm_train: null stats");
+  if (seg_off == nullptr)
+    return group_norm_impl(x, n, c, groups, gamma, beta, eps, negative_slope, out, nullptr, 1, n, ws, ws_bytes,
+                           static_cast<hipStream_t>(stream_), residual, stats);
+  GR_REQUIRE(nseg >= 0 && nseg < 65536 && max_seg_rows >= 0, "group_norm_train: bad segments");
+  return group_norm_impl(x, n, c, groups, gamma, beta, eps, negative_slope, out, seg_off, nseg, max_seg_rows, ws, ws_bytes,
+                         static_cast<hipStream_t>(stream_), residual, stats);
 }

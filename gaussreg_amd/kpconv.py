@@ -47,7 +47,7 @@ _mode = threading.local()
 
 
 @contextlib.contextmanager
-def differentiable(chunk_rows=0):
+def differentiable(chunk_rows=0, fused_norm=False):
     """Inside this context, with grad mode on, `KPConv.forward`, `maxpool` and `nearest_upsample` run the same forward
     kernels as outside it and return tensors with a `grad_fn` whenever `s_feats` / `weights` / `bias` (or `x`) require
     grad; `KPConvFPN.forward` no longer switches grad off.  The transformer stack consults the same switch
@@ -56,9 +56,13 @@ def differentiable(chunk_rows=0):
     only in here: backbone, transformer, patch gather and fine matching become differentiable together.
     Points, kernel points and indices get no gradient: a `q_points` / `s_points` that requires grad raises ValueError.
     Outside the context every call is inference, as before.  Thread-local.  `chunk_rows` > 0 overrides the number of
-    queries the KPConv backward processes per chunk (tests)."""
+    queries the KPConv backward processes per chunk (tests).
+    `fused_norm=True` (opt-in) also runs the backbone's GroupNorm layers in HIP, forward and backward
+    (kpconv_blocks.GroupNorm: gr_group_norm_train / gr_group_norm_backward, with the residual add and the LeakyReLU of a
+    block's tail fused); `kpconv_blocks.norm_segments` is then accepted, so several pairs train in one pass.  With the
+    default every layer takes the torch path it took before, bit for bit."""
     old = getattr(_mode, "state", None)
-    _mode.state = (True, int(chunk_rows))
+    _mode.state = (True, int(chunk_rows), bool(fused_norm))
     try:
         yield
     finally:
@@ -68,6 +72,12 @@ def differentiable(chunk_rows=0):
 def differentiable_active():
     """True inside `differentiable()` while grad mode is on."""
     return getattr(_mode, "state", None) is not None and torch.is_grad_enabled()
+
+
+def fused_norm_active():
+    """True inside `differentiable(fused_norm=True)` while grad mode is on."""
+    state = getattr(_mode, "state", None)
+    return state is not None and state[2] and torch.is_grad_enabled()
 
 
 def no_grad_unless_differentiable(fn):

@@ -1,12 +1,13 @@
 """Mirror of geotransformer/modules/kpconv/modules.py (inference; trainable inside `kpconv.differentiable()`): the blocks KPConvFPN is assembled from
-(backbone.py:95-162), with the HIP KPConv / maxpool / nearest_upsample / GroupNorm inside.  Sub-module names and parameter
+(backbone.py:95-162), with the HIP KPConv / maxpool / nearest_upsample / GroupNorm inside.  Inside
+`kpconv.differentiable(fused_norm=True)` the GroupNorm is HIP in training too (`_GroupNormFunction`).  Sub-module names and parameter
 shapes follow the reference so its checkpoints load key for key (`KPConv.weights`, `norm.norm.weight`, `mlp.weight`, ...).
 nn.Linear stays the stock PyTorch-ROCm layer (rocBLAS), as in the reference."""
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .kpconv import KPConv, differentiable_active, maxpool, nearest_upsample
+from .kpconv import KPConv, differentiable_active, fused_norm_active, maxpool, nearest_upsample
 
 
 import contextlib
@@ -33,6 +34,52 @@ def norm_segments(table):
         _segments.table = old
 
 
+_SEGMENTS_REFUSED = ("norm_segments inside differentiable(): the torch GroupNorm that carries the gradient has no segments; "
+                     "train one pair per pass")
+
+
+class _GroupNormFunction(torch.autograd.Function):
+    """GroupNorm (+ residual, + LeakyReLU) of a (N, C) matrix per row segment with the HIP forward that keeps its statistics
+    (gr_group_norm_train: the bits of the inference kernels) and the HIP backward (gr_group_norm_backward).  Kept for the
+    backward: x, the output (its sign is the LeakyReLU mask; not kept when there is no activation), the (nseg, 2, G)
+    statistics and gamma -- neither the pre-activation nor the residual."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, residual, groups, eps, slope, seg_off, nseg, max_rows):
+        dev = x.device
+        x = x.contiguous()
+        n, c = x.shape
+        out = torch.empty_like(x)
+        stats = torch.empty((nseg, 2, groups), dtype=torch.float32, device=dev)
+        w = None if weight is None else weight.contiguous()
+        b = None if bias is None else bias.contiguous()
+        res = None if residual is None else residual.reshape(x.shape).contiguous()
+        _lib.call(dev, "gr_group_norm_train", x, n, c, groups, w, b, eps, slope, res, out, stats, seg_off, nseg, max_rows,
+                  ws=_lib.lib().gr_group_norm_seg_workspace_bytes(groups, nseg))
+        ctx.save_for_backward(x, out if slope != 1.0 else None, stats, w, seg_off)
+        ctx.args = (groups, slope, nseg, max_rows)
+        ctx.res_shape = None if residual is None else residual.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, out, stats, w, seg_off = ctx.saved_tensors
+        groups, slope, nseg, max_rows = ctx.args
+        need_x, need_w, need_b, need_res = ctx.needs_input_grad[:4]
+        dev = x.device
+        n, c = x.shape
+        go = grad_out.to(torch.float32).reshape(x.shape).contiguous()
+        gx = torch.empty_like(x) if need_x else None
+        gres = torch.empty_like(x) if need_res else None
+        gw = torch.empty(c, dtype=torch.float32, device=dev) if need_w else None
+        gb = torch.empty(c, dtype=torch.float32, device=dev) if need_b else None
+        _lib.call(dev, "gr_group_norm_backward", x, out, go, w, stats, n, c, groups, slope, seg_off, nseg, max_rows,
+                  gx, gres, gw, gb, ws=_lib.lib().gr_group_norm_backward_workspace_bytes(c, groups, nseg))
+        if gres is not None:
+            gres = gres.reshape(ctx.res_shape)
+        return gx, gw, gb, gres, None, None, None, None, None, None
+
+
 class GroupNorm(nn.Module):
     """modules.py:32-50: GroupNorm over the channel axis of a (N, C) point-feature matrix."""
 
@@ -45,12 +92,16 @@ class GroupNorm(nn.Module):
         """`negative_slope`: fuse the LeakyReLU that follows the norm in every block (None: plain GroupNorm).
         `residual` (same shape as x): added between the norm and the activation -- the tail of a residual block."""
         c = self.num_channels
-        if differentiable_active() and getattr(_segments, "table", None):
-            raise NotImplementedError("norm_segments inside differentiable(): the torch GroupNorm that carries the gradient "
-                                      "has no segments; train one pair per pass")
-        hip_ok = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and not torch.is_grad_enabled() and c % 4 == 0
-                  and ((c // 4 <= 256 and 256 % (c // 4) == 0) or (c // 4) % 256 == 0) and self.num_groups <= 64)
-        if not hip_ok:
+        fused = fused_norm_active()
+        if differentiable_active() and not fused and getattr(_segments, "table", None):
+            raise NotImplementedError(_SEGMENTS_REFUSED)
+        shape_ok = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and c % 4 == 0
+                    and ((c // 4 <= 256 and 256 % (c // 4) == 0) or (c // 4) % 256 == 0) and self.num_groups <= 64)
+        if fused and shape_ok:
+            return self._forward_fused(x, negative_slope, residual)
+        if not (shape_ok and not torch.is_grad_enabled()):
+            if fused and getattr(_segments, "table", None):    # a shape the kernels do not take: only torch is left
+                raise NotImplementedError(_SEGMENTS_REFUSED)
             y = self.norm(x.t().unsqueeze(0))     # (N, C) -> (1, C, N): statistics per group over all points
             y = y.squeeze(0).t().squeeze()        # the trailing squeeze() is the reference's (modules.py:50)
             if residual is not None:
@@ -81,6 +132,20 @@ class GroupNorm(nn.Module):
                       ws=L.gr_group_norm_seg_workspace_bytes(self.num_groups, nseg))
         else:
             _lib.call(dev, "gr_group_norm", *head, out, ws=L.gr_group_norm_workspace_bytes(self.num_groups))
+        return out.squeeze()
+
+    def _forward_fused(self, x, negative_slope, residual):
+        """Training inside differentiable(fused_norm=True): the inference kernels' output with a grad_fn."""
+        table = getattr(_segments, "table", None)
+        seg = table.get(x.shape[0]) if table else None
+        seg_off, max_rows = seg if seg is not None else (None, x.shape[0])
+        nseg = seg_off.numel() - 1 if seg is not None else 1
+        if residual is not None and residual.dtype != torch.float32:
+            residual = residual.float()
+        out = _GroupNormFunction.apply(x, self.norm.weight, self.norm.bias, residual, self.num_groups, float(self.norm.eps),
+                                       1.0 if negative_slope is None else float(negative_slope), seg_off, nseg, int(max_rows))
+        if residual is not None:
+            return out.reshape(torch.broadcast_shapes(out.squeeze().shape, residual.shape))
         return out.squeeze()
 
 
@@ -177,7 +242,7 @@ class ResidualBlock(nn.Module):
         h = _norm_act(self.norm_conv, x, self.leaky_relu.negative_slope)
         shortcut = maxpool(s_feats, neighbor_indices) if self.strided else s_feats
         sc = self.unary_shortcut(shortcut)
-        if isinstance(self.unary2.norm, GroupNorm) and not torch.is_grad_enabled():
+        if isinstance(self.unary2.norm, GroupNorm) and (not torch.is_grad_enabled() or fused_norm_active()):
             # unary2's GroupNorm (no activation), + shortcut, LeakyReLU: one apply pass instead of three
             y = self.unary2.mlp(h)
             if sc.shape == y.shape:
@@ -211,11 +276,11 @@ class KPConvFPN(nn.Module):
 
     def forward(self, feats, data_dict):
         """Inference (grad off) by default; inside `kpconv.differentiable()` with grad mode on, the whole backbone is
-        differentiable: HIP backward for KPConv / maxpool / nearest_upsample, torch autograd for the other layers."""
+        differentiable: HIP backward for KPConv / maxpool / nearest_upsample (and for GroupNorm with `fused_norm=True`,
+        which also admits a `norm_segments` table: several pairs in one pass), torch autograd for the other layers."""
         if differentiable_active():
-            if getattr(_segments, "table", None):
-                raise NotImplementedError("norm_segments inside differentiable(): the torch GroupNorm that carries the "
-                                          "gradient has no segments; train one pair per pass")
+            if getattr(_segments, "table", None) and not fused_norm_active():
+                raise NotImplementedError(_SEGMENTS_REFUSED)
             return self._forward(feats, data_dict)
         with torch.no_grad():
             return self._forward(feats, data_dict)
