@@ -20,9 +20,12 @@ def live_mask(B, M, N, row_masks, col_masks):
     return rl, cl, rl.unsqueeze(2) & cl.unsqueeze(1)
 
 
-def forward(scores, alpha, row_masks, col_masks, num_iterations, inf=1e12, keep=None):
+def forward(scores, alpha, row_masks, col_masks, num_iterations, inf=1e12, keep=None, marginal_dtype=None):
     """scores (B, M, N) and alpha (0-d) torch tensors of one dtype -> (B, M+1, N+1), learnable_sinkhorn.py:20-66 op for op.
-    `keep`: a dict that receives the padded matrix 'Z' (with retain_grad when it requires grad)."""
+    `keep`: a dict that receives the padded matrix 'Z' (with retain_grad when it requires grad).
+    `marginal_dtype`: the dtype the log-marginals and the normaliser are evaluated in before they join the scores (default:
+    the scores' own).  The reference module builds them in float32 whatever the scores are (learnable_sinkhorn.py:49-61:
+    `.float()` counts, `torch.empty` buffers), so its float64 evaluation is reproduced with torch.float32 here."""
     B, M, N = scores.shape
     dtype = scores.dtype
     rl, cl, live = live_mask(B, M, N, row_masks, col_masks)
@@ -33,8 +36,9 @@ def forward(scores, alpha, row_masks, col_masks, num_iterations, inf=1e12, keep=
         if Z.requires_grad:
             Z.retain_grad()
         keep["Z"] = Z
-    nvr = rl[:, :M].to(dtype).sum(1)
-    nvc = cl[:, :N].to(dtype).sum(1)
+    mdt = dtype if marginal_dtype is None else marginal_dtype
+    nvr = rl[:, :M].to(mdt).sum(1)
+    nvc = cl[:, :N].to(mdt).sum(1)
     norm = -torch.log(nvr + nvc)
     log_mu = norm.unsqueeze(1).repeat(1, M + 1)
     log_mu[:, M] = torch.log(nvc) + norm
@@ -42,6 +46,7 @@ def forward(scores, alpha, row_masks, col_masks, num_iterations, inf=1e12, keep=
     log_nu = norm.unsqueeze(1).repeat(1, N + 1)
     log_nu[:, N] = torch.log(nvr) + norm
     log_nu[~cl] = -inf
+    log_mu, log_nu, norm = log_mu.to(dtype), log_nu.to(dtype), norm.to(dtype)
     u, v = torch.zeros_like(log_mu), torch.zeros_like(log_nu)
     for _ in range(num_iterations):
         u = log_mu - torch.logsumexp(Z + v.unsqueeze(1), dim=2)
