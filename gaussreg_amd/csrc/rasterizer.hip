@@ -996,7 +996,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
     // ---- blend: each 16-lane group walks its own list
     const int len_cell = __shfl(tot_lane, (BLOCK / WAVE) * lw + lane / (CELL * CELL));  // cell = 4 lw + lane / 16
     const int n_cell = done ? 0 : len_cell;
-    // Two list entries per step, each read as {px, py, cx, cz} + {cy, op, pc, r} (+ {g, b} when it blends) and evaluated
+    // Two list entries per step, each read as {px, py, cx, cz} + {cy, op, pc, r} + {g, b} and evaluated
     // on its own registers: dx, dy, q, power, the exponential and alpha are the oracle's scalar sequence per entry (the
     // compiler may pack the two entries' independent operations); only the order-dependent tail (transmittance test,
     // colour accumulation) is serial.
@@ -1009,14 +1009,22 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
       pair = lp[i / 2 + 1];
       const float4 a0 = lds_at(s_ga, o0), b0 = lds_at(s_gb, o0);
       const float4 a1 = lds_at(s_ga, o1), b1 = lds_at(s_gb, o1);
-      // red is used only where the entry blends: without this the compiler splits {cy, op, pc, r} into a ds_read_b96
-      // (8 LDS cycles) and a ds_read_b32 under the branch (2 more) instead of one ds_read_b128 (4)
-      asm volatile("" ::"v"(b0.w), "v"(b1.w));
+      // {g, b} of both entries are read here, with the records, and not where an entry blends: the serial tail of the
+      // step then holds no LDS read and no wait for one (z, AUX only, stays under the branch: the instance with AUX
+      // and KEEP has no register left for it).
+      const f32x2 c0 = lds_at(s_gc, o0 / 2), c1 = lds_at(s_gc, o1 / 2);
+      // red and the cutoff are not used up to alpha: without this the compiler splits {cy, op, pc, r} into a ds_read_b64
+      // and a ds_read_b32 instead of one ds_read_b128
+      asm volatile("" ::"v"(b0.w), "v"(b1.w), "v"(b0.z), "v"(b1.z));
       float power0, power1;
       const float alpha0 = entry_alpha<FAST_EXP>(a0, b0.x, b0.y, pf, power0);
       const float alpha1 = entry_alpha<FAST_EXP>(a1, b1.x, b1.y, pf, power1);
-      const bool ok0 = !(power0 > 0.0f) && !(power0 < b0.z) && !(alpha0 < 1.0f / 255.0f);
-      const bool ok1 = !(power1 > 0.0f) && !(power1 < b1.z) && !(alpha1 < 1.0f / 255.0f);
+      // the colours have arrived by now: the wait for them stands here, once, in front of the two predicated regions
+      asm volatile("" ::"v"(c0.x), "v"(c0.y), "v"(c1.x), "v"(c1.y), "v"(alpha0), "v"(alpha1));
+      // The oracle's two tests.  The cutoff `power < pc` is not tested here: it only ever skips what `alpha < 1/255` skips
+      // (see the load above), alpha is computed either way, and the pad entry (opacity 0) has alpha = 0.
+      const bool ok0 = !(power0 > 0.0f) && !(alpha0 < 1.0f / 255.0f);
+      const bool ok1 = !(power1 > 0.0f) && !(alpha1 < 1.0f / 255.0f);
       // A pixel that saturates leaves the walk through the loop condition, not through a `break`: the wave's control flow
       // stays one counted loop with two predicated regions.
       if (ok0) {
@@ -1026,7 +1034,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         } else {
           const float w = alpha0 * T;
           C0 = fmaf(b0.w, w, C0);
-          C12 = __builtin_elementwise_fma(lds_at(s_gc, o0 / 2), f32x2{w, w}, C12);
+          C12 = __builtin_elementwise_fma(c0, f32x2{w, w}, C12);
           if (AUX) Dz = fmaf(lds_at(s_z, o0 / 4), w, Dz);
           T = test_T;
           if (KEEP) last = batch_base + (int)(o0 / 16) + 1;
@@ -1039,7 +1047,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
         } else {
           const float w = alpha1 * T;
           C0 = fmaf(b1.w, w, C0);
-          C12 = __builtin_elementwise_fma(lds_at(s_gc, o1 / 2), f32x2{w, w}, C12);
+          C12 = __builtin_elementwise_fma(c1, f32x2{w, w}, C12);
           if (AUX) Dz = fmaf(lds_at(s_z, o1 / 4), w, Dz);
           T = test_T;
           if (KEEP) last = batch_base + (int)(o1 / 16) + 1;
