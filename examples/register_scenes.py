@@ -11,6 +11,8 @@ the GPU through gaussreg_amd:
 
     python examples/register_scenes.py --ref_file A/point_cloud.ply --src_file B/point_cloud.ply --weights ckpt.pth.tar
     python examples/register_scenes.py --synthetic            # two views of one synthetic scene, random-init network
+    python examples/register_scenes.py --synthetic --evaluate # ... scored against the known transform: overlap, inlier
+                                                              # ratio, modified chamfer distance (gaussreg_amd.cloud_nn)
 
 Without --weights the network runs on random weights (the stages run, the estimate is meaningless); the reference's
 checkpoint format (`state_dict["model"]`, demo.py:141-142) loads as is.
@@ -80,6 +82,8 @@ def main():
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--render", type=int, default=0, help="render this many views of the fused scene (orbit around its centre)")
     ap.add_argument("--render_size", default="640x480")
+    ap.add_argument("--evaluate", action="store_true", help="with --synthetic: score the result against the known transform")
+    ap.add_argument("--eval_radius", type=float, default=0.1, help="positive radius of --evaluate, in scene units")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     os.makedirs(args.output_path, exist_ok=True)
@@ -88,6 +92,8 @@ def main():
         args.ref_file, args.src_file, T_gt = synthetic_scene_pair(args.output_path)
     elif not (args.ref_file and args.src_file):
         ap.error("--ref_file and --src_file (or --synthetic) are required")
+    if args.evaluate and T_gt is None:
+        ap.error("--evaluate needs the ground truth of --synthetic")
     t0 = time.perf_counter()
     rec_ref = torch.from_numpy(gs_io.read_gs_ply(args.ref_file)).to(dev)
     rec_src = torch.from_numpy(gs_io.read_gs_ply(args.src_file)).to(dev)
@@ -119,9 +125,28 @@ def main():
     print("estimated transform (src -> ref):\n", np.array_str(T, precision=4, suppress_small=True))
     if T_gt is not None:
         print("ground truth:\n", np.array_str(T_gt, precision=4, suppress_small=True))
+    if args.evaluate:
+        evaluate(rp, sp, out, pair, T_gt, T, args.eval_radius)
     if args.render > 0:
         render_fused(fused, args.render, args.render_size, args.output_path)
     return T
+
+
+def evaluate(ref_points, src_points, out, pair, T_gt, T_est, radius):
+    """The reference's evaluation of a pair with known ground truth, in the frame of the original scenes: the overlap of the
+    sampled clouds under the ground truth, the share of the predicted correspondences that the ground truth brings within
+    `radius`, and the modified chamfer distance of the estimate (the ref cloud stands in for the clean cloud)."""
+    from gaussreg_amd import cloud_nn
+    ref_points, src_points = ref_points.float().contiguous(), src_points.float().contiguous()
+    ref_corr = (out["ref_corr_points"] / pair["ref_adjust_scale"] + pair["ref_center"]).float().contiguous()
+    src_corr = (out["src_corr_points"] / pair["src_adjust_scale"] + pair["src_center"]).float().contiguous()
+    overlap = cloud_nn.compute_overlap(ref_points, src_points, T_gt, positive_radius=radius)
+    inlier = cloud_nn.compute_inlier_ratio(ref_corr, src_corr, T_gt, positive_radius=radius) if ref_corr.shape[0] else 0.0
+    chamfer = cloud_nn.compute_modified_chamfer_distance(ref_points, ref_points, src_points, T_gt, T_est)
+    print(f"evaluation at radius {radius:g}:")
+    print(f"  overlap: {overlap:.4f}")
+    print(f"  inlier ratio: {inlier:.4f}  ({ref_corr.shape[0]} correspondences)")
+    print(f"  modified chamfer distance: {chamfer:.6f}")
 
 
 def render_fused(fused, n_views, size, output_path):

@@ -19,10 +19,18 @@ def differentiable(chunk_rows=0, fused_norm=False):
 
 _LOSSES = ("WeightedCircleLoss", "CoarseMatchingLoss", "FineMatchingLoss", "OverallLoss", "Evaluator")
 
+# the reference's overlap / correspondence / evaluation functions on the cross-cloud search (gaussreg_amd.cloud_nn)
+_CLOUD_NN = ("compute_overlap", "get_correspondences", "compute_modified_chamfer_distance", "compute_inlier_ratio",
+             "compute_correspondence_residual", "evaluate_correspondences", "compute_registration_rmse")
+
 
 def __getattr__(name):
-    """The training losses and metrics (gaussreg_amd.loss), imported on first use like `differentiable`."""
+    """The training losses and metrics (gaussreg_amd.loss) and the evaluation functions (gaussreg_amd.cloud_nn), imported on
+    first use like `differentiable`."""
     if name in _LOSSES:
         from . import loss
         return getattr(loss, name)
+    if name in _CLOUD_NN:
+        from . import cloud_nn
+        return getattr(cloud_nn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -39,6 +39,27 @@ def upstream_names(package, submodule, names, namespace):
     return True
 
 
+def inline_shadowed(namespace):
+    """Call as `inline_shadowed(globals())` at the TOP of an alias sub-module that replaces a few names of a file whose other
+    names callers import from the same module path (`geotransformer.utils.registration`): the same-named file in a later
+    entry of the parent package's `__path__` is executed in `namespace`, so what it defines belongs to the alias module
+    itself (`__module__` is the module path callers know), and the alias then defines its own names over it.  -> True when
+    a file was found and ran; False without one, or when it could not import what it needs (its names are then absent)."""
+    parent, _, leaf = namespace["__name__"].rpartition(".")
+    here = os.path.dirname(os.path.abspath(namespace["__file__"]))
+    for d in list(getattr(sys.modules.get(parent), "__path__", [])):
+        cand = os.path.join(d, leaf + ".py")
+        if os.path.abspath(d) != here and os.path.isfile(cand):
+            with open(cand) as fh:
+                code = compile(fh.read(), cand, "exec")
+            try:
+                exec(code, namespace)
+            except ImportError:
+                return False
+            return True
+    return False
+
+
 def shadowed_module(alias_name, alias_file):
     """The module a sub-module alias of this repo shadows: the same file name in a LATER entry of the parent package's
     `__path__`, loaded under `<alias_name>__upstream` (None when there is none).  Lets an alias sub-module re-export the
