@@ -13,6 +13,8 @@ the GPU through gaussreg_amd:
     python examples/register_scenes.py --synthetic            # two views of one synthetic scene, random-init network
     python examples/register_scenes.py --synthetic --evaluate # ... scored against the known transform: overlap, inlier
                                                               # ratio, modified chamfer distance (gaussreg_amd.cloud_nn)
+    python examples/register_scenes.py --synthetic --icp      # ... the coarse transform refined by point-to-point ICP on ALL
+                                                              # Gaussian centres (gaussreg_amd.icp) before the scenes are fused
 
 Without --weights the network runs on random weights (the stages run, the estimate is meaningless); the reference's
 checkpoint format (`state_dict["model"]`, demo.py:141-142) loads as is.
@@ -84,12 +86,16 @@ def main():
     ap.add_argument("--render_size", default="640x480")
     ap.add_argument("--evaluate", action="store_true", help="with --synthetic: score the result against the known transform")
     ap.add_argument("--eval_radius", type=float, default=0.1, help="positive radius of --evaluate, in scene units")
+    ap.add_argument("--synthetic_n", type=int, default=400_000, help="Gaussians of the --synthetic scene")
+    ap.add_argument("--icp", action="store_true", help="refine the coarse transform by ICP on all Gaussian centres before fusing")
+    ap.add_argument("--icp_dist", type=float, default=0.1, help="largest correspondence distance of --icp, in scene units")
+    ap.add_argument("--icp_scale", action="store_true", help="--icp fits a uniform scale as well")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     os.makedirs(args.output_path, exist_ok=True)
     T_gt = None
     if args.synthetic:
-        args.ref_file, args.src_file, T_gt = synthetic_scene_pair(args.output_path)
+        args.ref_file, args.src_file, T_gt = synthetic_scene_pair(args.output_path, n=args.synthetic_n)
     elif not (args.ref_file and args.src_file):
         ap.error("--ref_file and --src_file (or --synthetic) are required")
     if args.evaluate and T_gt is None:
@@ -116,6 +122,9 @@ def main():
     t2 = time.perf_counter()
     T = gs_points.denormalize_transform(out["estimated_transform"], pair["ref_center"], pair["src_center"],
                                         pair["ref_adjust_scale"], pair["src_adjust_scale"])
+    T_coarse = T
+    if args.icp:
+        T = refine_icp(rec_ref, rec_src, T, args.icp_dist, args.icp_scale)
     np.savez(os.path.join(args.output_path, "estimated_transform.npz"), estimated_transform=T)
     fused = gs_io.gaussian_fuse_records(rec_ref, rec_src, T)
     gs_io.write_gs_ply(os.path.join(args.output_path, "fused.ply"), fused.cpu().numpy())
@@ -127,6 +136,8 @@ def main():
         print("ground truth:\n", np.array_str(T_gt, precision=4, suppress_small=True))
     if args.evaluate:
         evaluate(rp, sp, out, pair, T_gt, T, args.eval_radius)
+        if args.icp:
+            evaluate_refinement(rec_ref, rec_src, T_gt, T_coarse, T, args.eval_radius)
     if args.render > 0:
         render_fused(fused, args.render, args.render_size, args.output_path)
     return T
@@ -147,6 +158,40 @@ def evaluate(ref_points, src_points, out, pair, T_gt, T_est, radius):
     print(f"  overlap: {overlap:.4f}")
     print(f"  inlier ratio: {inlier:.4f}  ({ref_corr.shape[0]} correspondences)")
     print(f"  modified chamfer distance: {chamfer:.6f}")
+
+
+def refine_icp(rec_ref, rec_src, T, max_dist, with_scale):
+    """Point-to-point ICP from the coarse transform on the centres of ALL Gaussians of the two scenes (the network saw a
+    sample of them); -> the refined (4, 4) float64 transform, or the coarse one when the refinement matches fewer points."""
+    from gaussreg_amd import icp
+    ref, src = rec_ref[:, :3].float().contiguous(), rec_src[:, :3].float().contiguous()
+    res = icp(src, ref, T, max_dist=max_dist, with_scale=with_scale, return_history=True)
+    start = res.history[0]
+    print(f"icp ({res.status}, {res.iterations} iterations, max_dist {max_dist:g}): fitness {float(start[14]):.4f} -> {res.fitness:.4f}, "
+          f"inlier rmse {float(start[15]):.6f} -> {res.inlier_rmse:.6f}")
+    if res.iterations == 0 or res.fitness < float(start[14]):
+        print("icp: the coarse transform is kept")
+        return T
+    return res.transform.double().cpu().numpy()
+
+
+def _motion_errors(T, T_gt):
+    s, s_gt = np.cbrt(np.linalg.det(T[:3, :3])), np.cbrt(np.linalg.det(T_gt[:3, :3]))
+    R = (T[:3, :3] / s) @ (T_gt[:3, :3] / s_gt).T
+    angle = np.degrees(np.arccos(np.clip((np.trace(R) - 1.0) / 2.0, -1.0, 1.0)))
+    return angle, np.linalg.norm(T[:3, 3] - T_gt[:3, 3]), s / s_gt
+
+
+def evaluate_refinement(rec_ref, rec_src, T_gt, T_coarse, T_refined, radius):
+    """The registration errors against the known transform and the overlap of the full scenes, before and after --icp."""
+    from gaussreg_amd import cloud_nn
+    ref, src = rec_ref[:, :3].float().contiguous(), rec_src[:, :3].float().contiguous()
+    print("refinement by icp:")
+    for label, T in (("coarse", T_coarse), ("refined", T_refined)):
+        angle, shift, scale = _motion_errors(np.asarray(T, np.float64), T_gt)
+        print(f"  {label} rotation error: {angle:.4f} deg, translation error: {shift:.5f}, scale ratio: {scale:.5f}")
+        print(f"  {label} registration rmse: {cloud_nn.compute_registration_rmse(src, T_gt, T):.6f}")
+        print(f"  {label} overlap: {cloud_nn.compute_overlap(ref, src, T, positive_radius=radius):.4f}")
 
 
 def render_fused(fused, n_views, size, output_path):

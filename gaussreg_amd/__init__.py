@@ -23,10 +23,18 @@ _LOSSES = ("WeightedCircleLoss", "CoarseMatchingLoss", "FineMatchingLoss", "Over
 _CLOUD_NN = ("compute_overlap", "get_correspondences", "compute_modified_chamfer_distance", "compute_inlier_ratio",
              "compute_correspondence_residual", "evaluate_correspondences", "compute_registration_rmse")
 
+# point-to-point ICP (gaussreg_amd.icp).  `gaussreg_amd.icp` is the submodule, which is callable as its function `icp`:
+# `gaussreg_amd.icp(src, ref, ...)` and `from gaussreg_amd import icp; icp(src, ref, ...)` both run it.
+_ICP = ("icp", "evaluate_registration", "IcpResult")
+
 
 def __getattr__(name):
-    """The training losses and metrics (gaussreg_amd.loss) and the evaluation functions (gaussreg_amd.cloud_nn), imported on
-    first use like `differentiable`."""
+    """The training losses and metrics (gaussreg_amd.loss), the evaluation functions (gaussreg_amd.cloud_nn) and ICP
+    (gaussreg_amd.icp), imported on first use like `differentiable`."""
+    if name in _ICP:
+        import importlib
+        module = importlib.import_module(".icp", __name__)
+        return module if name == "icp" else getattr(module, name)
     if name in _LOSSES:
         from . import loss
         return getattr(loss, name)

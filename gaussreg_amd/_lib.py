@@ -6,7 +6,8 @@ that came after that header was closed are in include/gaussreg_hip_train.h, read
 TRAIN_DEFINES, and those of the matching stage in include/gaussreg_hip_train_matching.h into MATCH_TRAIN_SIGNATURES /
 MATCH_TRAIN_DEFINES, and those of the backbone's normalisation layers in include/gaussreg_hip_train_backbone.h into
 BACKBONE_TRAIN_SIGNATURES / BACKBONE_TRAIN_DEFINES, and the cross-cloud nearest-neighbour entry points of
-include/gaussreg_hip_cloud.h into CLOUD_SIGNATURES / CLOUD_DEFINES; `lib()` binds the five tables.  Only the three structs
+include/gaussreg_hip_cloud.h into CLOUD_SIGNATURES / CLOUD_DEFINES, and point-to-point ICP of include/gaussreg_hip_icp.h into
+ICP_SIGNATURES / ICP_DEFINES; `lib()` binds the six tables.  Only the three structs
 that cross the boundary are mirrored by hand (they hold arrays).  A declaration the parser does not understand raises.
 
 `call` is the one way a wrapper enters the library: it turns tensors into device pointers after checking that they are
@@ -23,6 +24,7 @@ TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train.h")
 MATCH_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train_matching.h")   # ... of the matching stage
 BACKBONE_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train_backbone.h")   # ... of the backbone's norms
 CLOUD_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_cloud.h")   # cross-cloud nearest neighbours
+ICP_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_icp.h")   # point-to-point ICP
 
 _lib = None
 
@@ -112,6 +114,8 @@ with open(BACKBONE_TRAIN_HEADER_PATH) as _f:
     BACKBONE_TRAIN_SIGNATURES, BACKBONE_TRAIN_DEFINES = parse_header(_f.read())
 with open(CLOUD_HEADER_PATH) as _f:
     CLOUD_SIGNATURES, CLOUD_DEFINES = parse_header(_f.read())
+with open(ICP_HEADER_PATH) as _f:
+    ICP_SIGNATURES, ICP_DEFINES = parse_header(_f.read())
 
 GR_PENDING = DEFINES["GR_PENDING"]        # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
 GR_RETRY_FULL = DEFINES["GR_RETRY_FULL"]  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward
@@ -119,6 +123,7 @@ GR_RETRY_BIN = DEFINES["GR_RETRY_BIN"]    # gr_raster_forward: bin buffer too sm
 GS_ADAM_MAX_GROUPS = DEFINES["GR_GS_ADAM_MAX_GROUPS"]
 GS_KNN_MAX_K = DEFINES["GR_GS_KNN_MAX_K"]
 CLOUD_KNN_MAX_K = CLOUD_DEFINES["GR_CLOUD_KNN_MAX_K"]
+CLOUD_ICP_MAX_ITERATIONS = ICP_DEFINES["GR_CLOUD_ICP_MAX_ITERATIONS"]
 GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = (DEFINES["GR_GS_DENSIFY_" + r] for r in ("CARRIED", "XYZ", "SCALING"))
 
 
@@ -141,7 +146,7 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                    + list(MATCH_TRAIN_SIGNATURES.items()) + list(BACKBONE_TRAIN_SIGNATURES.items())
-                                   + list(CLOUD_SIGNATURES.items())):
+                                   + list(CLOUD_SIGNATURES.items()) + list(ICP_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

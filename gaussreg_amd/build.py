@@ -39,7 +39,8 @@ def build(force=False, verbose=False):
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
     headers += [os.path.join(HERE, "..", "include", h) for h in ("gaussreg_hip.h", "gaussreg_hip_train.h",
                                                                  "gaussreg_hip_train_matching.h",
-                                                                 "gaussreg_hip_train_backbone.h", "gaussreg_hip_cloud.h")]
+                                                                 "gaussreg_hip_train_backbone.h", "gaussreg_hip_cloud.h",
+                                                                 "gaussreg_hip_icp.h")]
     jobs = []
     objs = []
     for src in sources():

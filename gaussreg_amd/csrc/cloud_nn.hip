@@ -44,28 +44,16 @@
 #include <cmath>
 
 #include "../../include/gaussreg_hip_cloud.h"
-#include "common.hpp"
+#include "cloud_grid.hpp"
 
 namespace gr {
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int QUERY_THREADS = 128;
-constexpr int DMAX = 128;            // cells per axis, at most
 constexpr int SAMPLES = 4096;        // per axis, for the quantiles
 constexpr int SORT_THREADS = 1024;
-constexpr int MAX_SHELLS = 8;
-constexpr int FALLBACK_BLOCKS = 4096;  // of THREADS / WAVE waves each, striding over the list
 constexpr int SHORT_ROW = 32;        // radius rows of at most this many hits are ordered by one lane
-constexpr int32_t NONE = 0x7fffffff;
-constexpr int MISC = 12;             // ints of small per-call state behind the cell tables
 constexpr int BOX_BLOCKS = 256;
 constexpr double POINTS_PER_CELL = 3.0;
-
-int grid_dim(int64_t n) {
-  int d = (int)std::floor(std::cbrt((double)n / POINTS_PER_CELL));
-  return d < 1 ? 1 : d > DMAX ? DMAX : d;
-}
 
 // B: (3, DMAX) floats; B[a * DMAX + c], c in 1 .. D-1, ascending
 __global__ __launch_bounds__(SORT_THREADS) void cloud_boundaries_kernel(const float* __restrict__ points, int64_t n, int D,
@@ -93,16 +81,6 @@ __global__ __launch_bounds__(SORT_THREADS) void cloud_boundaries_kernel(const fl
     }
   }
   for (int c = 1 + threadIdx.x; c < D; c += SORT_THREADS) B[a * DMAX + c] = ord2f(key[(int64_t)c * SAMPLES / D]);
-}
-
-// #{c in 1 .. D-1 : b[c] <= x}
-__device__ __forceinline__ int axis_cell(const float* b, int D, float x) {
-  int lo = 0, hi = D - 1;
-  while (lo < hi) {
-    const int mid = (lo + hi + 1) >> 1;
-    if (b[mid] <= x) lo = mid; else hi = mid - 1;
-  }
-  return lo;
 }
 
 __global__ __launch_bounds__(THREADS) void cloud_cell_kernel(const float* __restrict__ points, int64_t n, int D,
@@ -141,14 +119,6 @@ __global__ __launch_bounds__(THREADS) void cloud_box_kernel(const float* __restr
   }
 }
 
-// fl(g g) for the distance of q from the support's extent [lo, hi] on one axis, 0 inside it: every support point p has
-// fl((p - q)^2) >= it, by the monotonicity the face bound rests on
-__device__ __forceinline__ float axis_base(const uint32_t* __restrict__ box, int a, float q) {
-  const float lo = ord2f(~box[a]), hi = ord2f(box[3 + a]);
-  const float g = q < lo ? lo - q : q > hi ? q - hi : 0.f;
-  return g * g;
-}
-
 // sorted_cell: null for the support, whose cells nobody asks for again
 __global__ __launch_bounds__(THREADS) void cloud_scatter_kernel(const float* __restrict__ points, int64_t n,
                                                                 const int32_t* __restrict__ cell,
@@ -160,70 +130,6 @@ __global__ __launch_bounds__(THREADS) void cloud_scatter_kernel(const float* __r
   const int32_t pos = start[c] + atomicAdd(&cursor[c], 1);
   sorted[pos] = make_float4(points[3 * i], points[3 * i + 1], points[3 * i + 2], __int_as_float((int32_t)i));
   if (sorted_cell) sorted_cell[pos] = c;
-}
-
-// insert (d, j) into the ascending list of the CAP best under the order (d, j); indices are compile-time after unrolling
-template <int CAP>
-__device__ __forceinline__ void consider(float (&bd)[CAP], int32_t (&bj)[CAP], float d, int32_t j) {
-  if (d < bd[CAP - 1] || (d == bd[CAP - 1] && j < bj[CAP - 1])) {
-    bd[CAP - 1] = d;
-    bj[CAP - 1] = j;
-#pragma unroll
-    for (int t = CAP - 1; t > 0; --t) {
-      const bool up = bd[t] < bd[t - 1] || (bd[t] == bd[t - 1] && bj[t] < bj[t - 1]);
-      const float d0 = bd[t - 1], d1 = bd[t];
-      const int32_t j0 = bj[t - 1], j1 = bj[t];
-      bd[t - 1] = up ? d1 : d0;
-      bd[t] = up ? d0 : d1;
-      bj[t - 1] = up ? j1 : j0;
-      bj[t] = up ? j0 : j1;
-    }
-  }
-}
-
-template <int CAP>
-__device__ __forceinline__ void scan_range(const float4* __restrict__ sorted, int32_t begin, int32_t end, float qx, float qy,
-                                           float qz, float cap, float (&bd)[CAP], int32_t (&bj)[CAP]) {
-  for (int32_t s = begin; s < end; ++s) {
-    const float4 p = sorted[s];
-    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
-    const float d = (dx * dx + dy * dy) + dz * dz;
-    if (d <= cap) consider<CAP>(bd, bj, d, __float_as_int(p.w));
-  }
-}
-
-// cells [L, H] of one axis that a point with d <= cap can lie in; c = the query's cell
-__device__ __forceinline__ void axis_reach(const float* __restrict__ b, int D, int c, float q, float cap, int& L, int& H) {
-  if (cap == INFINITY) {
-    L = 0;
-    H = D - 1;
-    return;
-  }
-  L = H = c;
-  while (H + 1 <= D - 1) {  // cell H + 1 begins at b[H + 1] > q
-    const float g = b[H + 1] - q;
-    if (!(g * g <= cap)) break;
-    ++H;
-  }
-  while (L - 1 >= 0) {  // cell L - 1 ends at b[L] <= q
-    const float g = q - b[L];
-    if (!(g * g <= cap)) break;
-    --L;
-  }
-}
-
-// fl(g g) of the two faces of one axis behind which there are cells of the block [L, H]
-__device__ __forceinline__ float axis_bound(const float* __restrict__ b, int L, int H, int c, int r, float q) {
-  float bound = INFINITY;
-  if (c + r + 1 <= H) {
-    const float g = b[c + r + 1] - q;
-    bound = g * g;
-  }
-  if (c - r - 1 >= L) {
-    const float g = q - b[c - r];
-    bound = fminf(bound, g * g);
-  }
-  return bound;
 }
 
 template <int CAP>
@@ -245,12 +151,6 @@ __global__ __launch_bounds__(QUERY_THREADS) void cloud_knn_query_kernel(
   if (s >= nq) return;
   const float4 q = q_sorted[s];
   const int32_t c = q_sorted_cell[s];
-  const int cx = c % D, cy = (c / D) % D, cz = c / (D * D);
-  int Lx, Hx, Ly, Hy, Lz, Hz;
-  axis_reach(B, D, cx, q.x, cap, Lx, Hx);
-  axis_reach(B + DMAX, D, cy, q.y, cap, Ly, Hy);
-  axis_reach(B + 2 * DMAX, D, cz, q.z, cap, Lz, Hz);
-  const float base_x = axis_base(box, 0, q.x), base_y = axis_base(box, 1, q.y), base_z = axis_base(box, 2, q.z);
   float bd[CAP];
   int32_t bj[CAP];
 #pragma unroll
@@ -258,45 +158,13 @@ __global__ __launch_bounds__(QUERY_THREADS) void cloud_knn_query_kernel(
     bd[t] = INFINITY;
     bj[t] = NONE;
   }
-  for (int r = 0;; ++r) {
-    const int x0 = max(cx - r, Lx), x1 = min(cx + r, Hx);
-    const int y0 = max(cy - r, Ly), y1 = min(cy + r, Hy);
-    const int z0 = max(cz - r, Lz), z1 = min(cz + r, Hz);
-    for (int z = z0; z <= z1; ++z) {
-      for (int y = y0; y <= y1; ++y) {
-        const int32_t row = (z * D + y) * D;
-        if (z == cz - r || z == cz + r || y == cy - r || y == cy + r) {  // a face of the shell: cells x0 .. x1 are contiguous
-          scan_range<CAP>(s_sorted, s_start[row + x0], s_start[row + x1 + 1], q.x, q.y, q.z, cap, bd, bj);
-        } else {  // inside: the two end cells (r > 0 here)
-          if (cx - r >= Lx) scan_range<CAP>(s_sorted, s_start[row + cx - r], s_start[row + cx - r + 1], q.x, q.y, q.z, cap, bd, bj);
-          if (cx + r <= Hx) scan_range<CAP>(s_sorted, s_start[row + cx + r], s_start[row + cx + r + 1], q.x, q.y, q.z, cap, bd, bj);
-        }
-      }
-    }
-    // a point behind a face of axis a is at least the face away on a and at least the extent's distance on the others;
-    // the three lower bounds are added in d's own association, so the sum is a lower bound of d in fp32
-    const float fx = axis_bound(B, Lx, Hx, cx, r, q.x), fy = axis_bound(B + DMAX, Ly, Hy, cy, r, q.y),
-                fz = axis_bound(B + 2 * DMAX, Lz, Hz, cz, r, q.z);
-    const float bound = fminf((fx + base_y) + base_z, fminf((base_x + fy) + base_z, (base_x + base_y) + fz));
-    if (bd[CAP - 1] < bound) break;
-    if (x0 == Lx && x1 == Hx && y0 == Ly && y1 == Hy && z0 == Lz && z1 == Hz) break;  // the whole block has been scanned
-    if (r + 1 == MAX_SHELLS) {  // a wave of the second launch starts over and scans every point
-      list[atomicAdd(list_count, 1)] = (int32_t)s;
-      return;
-    }
+  if (!shell_search<CAP>(s_sorted, s_start, B, box, D, c, q.x, q.y, q.z, cap, bd, bj)) {
+    list[atomicAdd(list_count, 1)] = (int32_t)s;  // a wave of the second launch starts over and scans every point
+    return;
   }
   const int64_t qi = __float_as_int(q.w);
 #pragma unroll
   for (int t = 0; t < CAP; ++t) write_row<CAP>(dist2, index, qi, k, t, bd[t], bj[t]);
-}
-
-__device__ __forceinline__ uint64_t wave_min_u64(uint64_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const uint64_t u = __shfl_xor((unsigned long long)v, o);
-    v = u < v ? u : v;
-  }
-  return v;
 }
 
 template <int CAP>
@@ -450,7 +318,7 @@ struct CloudWorkspace {
 };
 
 CloudWorkspace carve_cloud(void* ws, int64_t nq, int64_t ns) {
-  const int D = grid_dim(ns);
+  const int D = cloud_grid_dim(ns);
   const size_t cells = (size_t)D * D * D;
   Carver c(ws);
   CloudWorkspace w;
@@ -478,29 +346,17 @@ bool clouds_ok(int64_t nq, int64_t ns) { return nq >= 0 && nq < (1ll << 31) && n
 
 // grid over the support, both clouds in cell order, the finiteness flag raised in w.misc[0]; nq >= 1
 int build_grids(const float* query, int64_t nq, const float* support, int64_t ns, const CloudWorkspace& w, hipStream_t stream) {
-  const int D = grid_dim(ns);
+  const int D = cloud_grid_dim(ns);
   const int64_t cells = (int64_t)D * D * D;
-  const unsigned sblocks = (unsigned)((ns + THREADS - 1) / THREADS), qblocks = (unsigned)((nq + THREADS - 1) / THREADS);
+  const unsigned qblocks = (unsigned)((nq + THREADS - 1) / THREADS);
   KernelTimer timer("cloud_nn_grid", stream);
-  GR_HIP(hipMemsetAsync(w.s_count, 0, w.zero_bytes, stream));
-  if (D > 1) {
-    hipLaunchKernelGGL(cloud_boundaries_kernel, dim3(3), dim3(SORT_THREADS), 0, stream, support, ns, D, w.B);
-    GR_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(cloud_box_kernel, dim3(sblocks < BOX_BLOCKS ? sblocks : BOX_BLOCKS), dim3(THREADS), 0, stream, support, ns,
-                     reinterpret_cast<uint32_t*>(w.misc + 4));
-  GR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_cell_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, D, w.B, w.s_cell, w.s_count, w.misc);
-  GR_LAUNCH_CHECK();
+  const SupportGrid g = {w.B, w.s_count, w.s_cursor, w.misc, w.scan_ws, w.s_cell, w.s_sorted};
+  int rc = cloud_build_support_grid(support, ns, g, w.s_count, w.zero_bytes, stream);
+  if (rc != GR_OK) return rc;
   hipLaunchKernelGGL(cloud_cell_kernel, dim3(qblocks), dim3(THREADS), 0, stream, query, nq, D, w.B, w.q_cell, w.q_count, w.misc);
   GR_LAUNCH_CHECK();
-  int rc = exclusive_scan_i32(w.s_count, w.s_count, cells + 1, 1, cells + 1, w.scan_ws, nullptr, stream);
-  if (rc != GR_OK) return rc;
   rc = exclusive_scan_i32(w.q_count, w.q_count, cells + 1, 1, cells + 1, w.scan_ws, nullptr, stream);
   if (rc != GR_OK) return rc;
-  hipLaunchKernelGGL(cloud_scatter_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, w.s_cell, w.s_count, w.s_cursor,
-                     w.s_sorted, (int32_t*)nullptr);
-  GR_LAUNCH_CHECK();
   hipLaunchKernelGGL(cloud_scatter_kernel, dim3(qblocks), dim3(THREADS), 0, stream, query, nq, w.q_cell, w.q_count, w.q_cursor,
                      w.q_sorted, w.q_sorted_cell);
   GR_LAUNCH_CHECK();
@@ -508,6 +364,35 @@ int build_grids(const float* query, int64_t nq, const float* support, int64_t ns
 }
 
 }  // namespace
+
+int cloud_grid_dim(int64_t n) {
+  int d = (int)std::floor(std::cbrt((double)n / POINTS_PER_CELL));
+  return d < 1 ? 1 : d > DMAX ? DMAX : d;
+}
+
+int cloud_build_support_grid(const float* support, int64_t ns, const SupportGrid& g, void* zero_from, size_t zero_bytes,
+                             hipStream_t stream) {
+  const int D = cloud_grid_dim(ns);
+  const int64_t cells = (int64_t)D * D * D;
+  const unsigned sblocks = (unsigned)((ns + THREADS - 1) / THREADS);
+  GR_HIP(hipMemsetAsync(zero_from, 0, zero_bytes, stream));
+  if (D > 1) {
+    hipLaunchKernelGGL(cloud_boundaries_kernel, dim3(3), dim3(SORT_THREADS), 0, stream, support, ns, D, g.B);
+    GR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(cloud_box_kernel, dim3(sblocks < BOX_BLOCKS ? sblocks : BOX_BLOCKS), dim3(THREADS), 0, stream, support, ns,
+                     reinterpret_cast<uint32_t*>(g.misc + 4));
+  GR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_cell_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, D, g.B, g.cell, g.count, g.misc);
+  GR_LAUNCH_CHECK();
+  const int rc = exclusive_scan_i32(g.count, g.count, cells + 1, 1, cells + 1, g.scan_ws, nullptr, stream);
+  if (rc != GR_OK) return rc;
+  hipLaunchKernelGGL(cloud_scatter_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, g.cell, g.count, g.cursor,
+                     g.sorted, (int32_t*)nullptr);
+  GR_LAUNCH_CHECK();
+  return GR_OK;
+}
+
 }  // namespace gr
 
 using namespace gr;
@@ -539,7 +424,7 @@ extern "C" int gr_cloud_knn(const float* query, int64_t nq, const float* support
   GR_HIP(hipStreamSynchronize(stream));
   GR_REQUIRE(h_flag == 0, "cloud knn: points must be finite");
   if (!dist2 && !index) return GR_OK;
-  const int D = grid_dim(ns);
+  const int D = cloud_grid_dim(ns);
   const unsigned qblocks = (unsigned)((nq + QUERY_THREADS - 1) / QUERY_THREADS);
   const int64_t waves = (nq + (THREADS / WAVE) - 1) / (THREADS / WAVE);
   const unsigned fblocks = (unsigned)(waves < FALLBACK_BLOCKS ? waves : FALLBACK_BLOCKS);
@@ -582,7 +467,7 @@ extern "C" int gr_cloud_radius_count(const float* query, int64_t nq, const float
   if (nq == 0) return GR_OK;
   const int rc = build_grids(query, nq, support, ns, w, stream);
   if (rc != GR_OK) return rc;
-  const int D = grid_dim(ns);
+  const int D = cloud_grid_dim(ns);
   const unsigned qblocks = (unsigned)((nq + QUERY_THREADS - 1) / QUERY_THREADS);
   {
     KernelTimer timer("cloud_nn_radius", stream);
@@ -629,7 +514,7 @@ extern "C" int gr_cloud_radius_pairs(const float* query, int64_t nq, const float
   GR_REQUIRE((int64_t)h_last == total, "cloud radius: total = %lld, the workspace holds a count of %d", (long long)total, h_last);
   if (total == 0) return GR_OK;
   GR_REQUIRE(row_scratch && pairs, "cloud radius: null row_scratch or pairs");
-  const int D = grid_dim(ns);
+  const int D = cloud_grid_dim(ns);
   const unsigned qblocks = (unsigned)((nq + QUERY_THREADS - 1) / QUERY_THREADS);
   const unsigned oblocks = (unsigned)((nq + THREADS - 1) / THREADS);
   KernelTimer timer("cloud_nn_radius", stream);

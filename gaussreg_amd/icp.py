@@ -1,0 +1,117 @@
+"""Point-to-point ICP on the HIP kernels of csrc/cloud_icp.hip: nearest-neighbour matching over a grid
+of the reference cloud that is built once, fp64 sums in a fixed order, the fp64 Umeyama fit (rigid, or rigid plus uniform
+scale) and the stop test, all on the device; one host read-back per call.
+
+    res = icp(src, ref, init_transform=T0, max_dist=0.1, with_scale=True)
+    res.transform            # (4, 4) fp32 on the device: maps src into ref's frame
+    res.fitness, res.inlier_rmse, res.iterations, res.converged, res.status
+    ev = evaluate_registration(src, ref, 0.1, T)      # the max_iterations=0 call: fitness and inlier_rmse of T
+
+Definition (include/gaussreg_hip_icp.h): a source point is transformed in fp32, ((A0 x + A1 y) + A2 z) + t, and matched to
+the reference point smallest under (d, j) among those with d <= float32(max_dist^2), exactly as `cloud_nn.knn` does;
+fitness = matched / all, inlier_rmse = sqrt(mean d) over the matched.  Every update is fitted to the ORIGINAL source
+coordinates.  The loop stops when fitness and inlier_rmse both change by less than their tolerances ("converged"), at
+max_iterations ("iteration_limit"), or when fewer than three points match or the fit has no spread ("degenerate": the
+transform is the last valid one).  Two calls give the same bits.  These are the semantics of Open3D's registration_icp
+with TransformationEstimationPointToPoint(with_scaling); parity with Open3D is unpinned.  There is no CPU fallback.
+"""
+import ctypes
+import sys
+import types
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .cloud_nn import _check_cloud, _finite, _r2
+
+MAX_ITERATIONS = _lib.CLOUD_ICP_MAX_ITERATIONS
+STATUS = {_lib.ICP_DEFINES["GR_CLOUD_ICP_CONVERGED"]: "converged",
+          _lib.ICP_DEFINES["GR_CLOUD_ICP_ITERATION_LIMIT"]: "iteration_limit",
+          _lib.ICP_DEFINES["GR_CLOUD_ICP_DEGENERATE"]: "degenerate"}
+
+
+@dataclass
+class IcpResult:
+    transform: torch.Tensor               # (4, 4) fp32 on the device
+    fitness: float
+    inlier_rmse: float
+    iterations: int
+    converged: bool
+    status: str                           # "converged", "iteration_limit" or "degenerate"
+    index: Optional[torch.Tensor] = None   # (N,) int64: the matched ref point of every src point, -1 for none
+    dist2: Optional[torch.Tensor] = None   # (N,) fp32: its squared distance, +inf for none
+    history: Optional[torch.Tensor] = None  # (iterations + 1, 16) fp64 on the host: T_t[12], n, S, fitness, rmse
+
+
+def _transform0(init_transform):
+    """-> (3, 4) fp32 numpy, contiguous: the upper rows of a (4, 4) transform given as a tensor, an array or nested lists."""
+    if init_transform is None:
+        return np.ascontiguousarray(np.eye(4, dtype=np.float32)[:3])
+    t = init_transform.detach().cpu().numpy() if isinstance(init_transform, torch.Tensor) else np.asarray(init_transform)
+    if t.shape != (4, 4):
+        raise ValueError(f"init_transform: shape {t.shape}, must be (4, 4)")
+    t = t.astype(np.float32)
+    if not np.isfinite(t).all():
+        raise ValueError("init_transform: every entry must be finite")
+    if not (t[3] == np.array([0, 0, 0, 1], np.float32)).all():
+        raise ValueError(f"init_transform: last row {t[3].tolist()}, must be [0, 0, 0, 1]")
+    return np.ascontiguousarray(t[:3])
+
+
+@torch.no_grad()
+def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=False, max_iterations=30,
+        relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False, return_history=False):
+    """Refine `init_transform` (None: identity) so that it maps src_points onto ref_points -> IcpResult."""
+    _check_cloud(src_points, "src_points")
+    _check_cloud(ref_points, "ref_points")
+    if ref_points.shape[0] < 1:
+        raise ValueError("ref_points: 0 points, at least 1")
+    if src_points.device != ref_points.device:
+        raise ValueError(f"src_points is on {src_points.device}, ref_points on {ref_points.device}")
+    if max_dist is None or not np.isfinite(float(max_dist)):
+        raise ValueError(f"max_dist = {max_dist!r} must be finite and >= 0")
+    cap = _r2(max_dist, "max_dist")
+    if not np.isfinite(cap):
+        raise ValueError(f"max_dist = {max_dist!r}: its square is not a finite float32")
+    if isinstance(max_iterations, bool) or not isinstance(max_iterations, int) or not 0 <= max_iterations <= MAX_ITERATIONS:
+        raise ValueError(f"max_iterations = {max_iterations!r} outside 0..{MAX_ITERATIONS}")
+    relative_fitness, relative_rmse = float(relative_fitness), float(relative_rmse)
+    if np.isnan(relative_fitness) or np.isnan(relative_rmse):
+        raise ValueError("relative_fitness and relative_rmse must not be NaN")
+    t0 = _transform0(init_transform)
+    src, ref = src_points.detach(), ref_points.detach()
+    dev, n, m = src.device, src.shape[0], ref.shape[0]
+    transform = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev) if return_correspondences else None
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
+    history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
+    h_status = (ctypes.c_int * 2)(0, 0)
+    _finite(lambda: _lib.call(dev, "gr_cloud_icp", src, n, ref, m, t0.ctypes.data_as(ctypes.c_void_p), cap, int(bool(with_scale)),
+                              max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history, h_status,
+                              ws=_lib.lib().gr_cloud_icp_workspace_bytes(n, m, max_iterations)))
+    status, iterations = STATUS[h_status[0]], int(h_status[1])
+    fitness, rmse = stats[:2].tolist()
+    return IcpResult(transform=transform, fitness=fitness, inlier_rmse=rmse, iterations=iterations,
+                     converged=status == "converged", status=status, index=index, dist2=dist2,
+                     history=history[:iterations + 1].cpu() if return_history else None)
+
+
+def evaluate_registration(src_points, ref_points, max_dist, transform=None, return_correspondences=False):
+    """Fitness and inlier RMSE of `transform` as it stands (Open3D's evaluate_registration): the max_iterations=0 call."""
+    return icp(src_points, ref_points, transform, max_dist=max_dist, max_iterations=0,
+               return_correspondences=return_correspondences)
+
+
+class _CallableModule(types.ModuleType):
+    """The package exports the function under the submodule's own name, so `gaussreg_amd.icp` is both: calling the module
+    calls `icp`."""
+
+    def __call__(self, *args, **kwargs):
+        return icp(*args, **kwargs)
+
+
+sys.modules[__name__].__class__ = _CallableModule
