@@ -60,8 +60,7 @@ __global__ __launch_bounds__(THREADS) void icp_key_kernel(const float* __restric
                                                           const float* __restrict__ B, uint64_t* __restrict__ keys,
                                                           int32_t* __restrict__ flag) {
   __shared__ float b[3 * DMAX];
-  for (int t = threadIdx.x; t < 3 * DMAX; t += THREADS) b[t] = (t % DMAX) >= 1 && (t % DMAX) < D ? B[t] : 0.f;
-  __syncthreads();
+  stage_boundaries(B, D, b);
   const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (i >= n) return;
   const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];

@@ -6,17 +6,18 @@
 // fp32, candidates ordered by (d, j), nothing excluded.  The order is total, so any search that meets every point that
 // can be among the answer gives the same bits.
 //
-// Search structure: the per-axis quantile grid of scene_init.hip, built over the SUPPORT: D x D x D cells,
-// boundaries B_a[1 .. D-1] are coordinates, cell_a(x) = #{c in 1 .. D-1 : B_a[c] <= x}.  The outermost cells are
-// unbounded, so a query that lies outside the support's bulk still lies INSIDE its cell and the face bound below needs no
-// special case for it.  The queries are put into cell order too (the same count / scan / scatter), so the lanes of a wave
-// walk neighbouring cells.
+// Search structure: the per-axis quantile grid of cloud_grid.hpp (where the shell loop, the face bound and its proof are),
+// built over the SUPPORT.  The outermost cells are unbounded, so a query that lies outside the support's bulk still lies
+// INSIDE its cell and the face bound needs no special case for it.  The queries are put into cell order too (the same
+// count / scan / scatter), so the lanes of a wave walk neighbouring cells.
 //
-//   cloud_boundaries_kernel   one workgroup per axis: 4096 strided samples of the support, bitonic sort in LDS;
+//   cloud_boundaries_kernel   one workgroup per axis: 4096 strided samples of the support, bitonic sort in LDS,
+//                             B_a[c] = sample[c 4096 / D];
 //   cloud_box_kernel          the support's exact bounding box (integer atomic max of order-preserving words);
 //   cloud_cell_kernel         one thread per point (either cloud): its cell, the cell's count, the finiteness flag;
 //   (exclusive_scan_i32 of the counts)
-//   cloud_scatter_kernel      one thread per point: (x, y, z, index) into cell order (integer atomic cursor);
+//   cloud_scatter_kernel      one thread per point: (x, y, z, index) into cell order (integer atomic cursor; the order
+//                             inside a cell varies from run to run and the result does not depend on it);
 //   cloud_knn_query_kernel<CAP>     one thread per cell-ordered query: Chebyshev shells of cells around its cell, CAP best
 //                                   in registers; a query that no rule stops within MAX_SHELLS shells is appended to a list;
 //   cloud_knn_fallback_kernel<CAP>  one WAVE per listed query: the 64 lanes walk strided parts of the whole support, each
@@ -25,22 +26,15 @@
 //                                   counts (EMIT = false) or writes the j of its hits in scan order (EMIT = true);
 //   cloud_radius_order_kernel       one lane per short row, the wave per long row: rank of every hit by j, (i, j) written.
 //
-// Face bound, exact in fp32 without slack (the proof of 3.9; the query need not be a support point).  A point in a cell
-// above c' on axis x has x_p >= B[c' + 1]; if B[c' + 1] >= x_q then, fp32 subtraction, multiplication and addition of
-// non-negative terms being monotone, d(q, p) >= fl(dx dx) >= fl(g g) with g = fl(B[c' + 1] - x_q); downwards x_p < B[c']
-// <= x_q gives the same with g = fl(x_q - B[c']).  Two uses:
+// What this search adds to the face bound (the query need not be a support point):
 //   * the cap: cells [L_a, H_a] per axis are those a point with d <= cap can lie in (walk outwards from the query's cell
 //     while fl(g g) <= cap: g grows with the distance, so the first failure ends the walk).  Everything outside that block
-//     is beyond the cap.  Without a cap the block is the whole grid.
-//   * the stop: after shell r the scanned block is cells [c - r, c + r] clamped to [L, H]; bound = min fl(g g) over the (at
-//     most six) faces that still have cells of the block behind them, each added -- in d's own association -- to the
-//     squared distance of the query from the support's bounding box on the two OTHER axes (0 for a query inside it): a
-//     point behind an x face is at least the face away in x and at least the box away in y and z.  For a query beside
-//     the support (the non-overlapping part of a pair) that term is what ends the search after the shell that holds its
-//     neighbours; the faces alone never would.  The search stops iff best[CAP - 1].d < bound
-//     (strictly: a point at the same distance with a lower index would displace it), or when the block is exhausted --
-//     which is also what "the bound exceeds the cap" comes to, because a face beyond the cap has no cell of the block
-//     behind it.
+//     is beyond the cap.  Without a cap the block is the whole grid.  "The bound exceeds the cap" needs no rule of its own:
+//     a face beyond the cap has no cell of the block behind it.
+//   * the box term: each face's fl(g g) is added -- in d's own association -- to the squared distance of the query from the
+//     support's bounding box on the two OTHER axes (0 for a query inside it): a point behind an x face is at least the
+//     face away in x and at least the box away in y and z.  For a query beside the support (the non-overlapping part of
+//     a pair) that term is what ends the search after the shell that holds its neighbours; the faces alone never would.
 #include <cmath>
 
 #include "../../include/gaussreg_hip_cloud.h"
@@ -87,8 +81,7 @@ __global__ __launch_bounds__(THREADS) void cloud_cell_kernel(const float* __rest
                                                              const float* __restrict__ B, int32_t* __restrict__ cell,
                                                              int32_t* __restrict__ count, int32_t* __restrict__ flag) {
   __shared__ float b[3 * DMAX];
-  for (int t = threadIdx.x; t < 3 * DMAX; t += THREADS) b[t] = (t % DMAX) >= 1 && (t % DMAX) < D ? B[t] : 0.f;
-  __syncthreads();
+  stage_boundaries(B, D, b);
   const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (i >= n) return;
   const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(THREADS) void cloud_box_kernel(const float* __restr
   }
 }
 
-// sorted_cell: null for the support, whose cells nobody asks for again
+// sorted_cell: null for a support whose cells nobody asks for again
 __global__ __launch_bounds__(THREADS) void cloud_scatter_kernel(const float* __restrict__ points, int64_t n,
                                                                 const int32_t* __restrict__ cell,
                                                                 const int32_t* __restrict__ start, int32_t* __restrict__ cursor,
@@ -153,11 +146,7 @@ __global__ __launch_bounds__(QUERY_THREADS) void cloud_knn_query_kernel(
   const int32_t c = q_sorted_cell[s];
   float bd[CAP];
   int32_t bj[CAP];
-#pragma unroll
-  for (int t = 0; t < CAP; ++t) {
-    bd[t] = INFINITY;
-    bj[t] = NONE;
-  }
+  clear_best<CAP>(bd, bj);
   if (!shell_search<CAP>(s_sorted, s_start, B, box, D, c, q.x, q.y, q.z, cap, bd, bj)) {
     list[atomicAdd(list_count, 1)] = (int32_t)s;  // a wave of the second launch starts over and scans every point
     return;
@@ -180,11 +169,7 @@ __global__ __launch_bounds__(THREADS) void cloud_knn_fallback_kernel(const float
     const float4 q = q_sorted[list[w]];
     float bd[CAP];
     int32_t bj[CAP];
-#pragma unroll
-    for (int t = 0; t < CAP; ++t) {
-      bd[t] = INFINITY;
-      bj[t] = NONE;
-    }
+    clear_best<CAP>(bd, bj);
     for (int64_t s = lane; s < ns; s += WAVE) {
       const float4 p = s_sorted[s];
       const float dx = p.x - q.x, dy = p.y - q.y, dz = p.z - q.z;
@@ -371,7 +356,7 @@ int cloud_grid_dim(int64_t n) {
 }
 
 int cloud_build_support_grid(const float* support, int64_t ns, const SupportGrid& g, void* zero_from, size_t zero_bytes,
-                             hipStream_t stream) {
+                             hipStream_t stream, bool with_box) {
   const int D = cloud_grid_dim(ns);
   const int64_t cells = (int64_t)D * D * D;
   const unsigned sblocks = (unsigned)((ns + THREADS - 1) / THREADS);
@@ -380,15 +365,17 @@ int cloud_build_support_grid(const float* support, int64_t ns, const SupportGrid
     hipLaunchKernelGGL(cloud_boundaries_kernel, dim3(3), dim3(SORT_THREADS), 0, stream, support, ns, D, g.B);
     GR_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(cloud_box_kernel, dim3(sblocks < BOX_BLOCKS ? sblocks : BOX_BLOCKS), dim3(THREADS), 0, stream, support, ns,
-                     reinterpret_cast<uint32_t*>(g.misc + 4));
-  GR_LAUNCH_CHECK();
+  if (with_box) {
+    hipLaunchKernelGGL(cloud_box_kernel, dim3(sblocks < BOX_BLOCKS ? sblocks : BOX_BLOCKS), dim3(THREADS), 0, stream, support,
+                       ns, reinterpret_cast<uint32_t*>(g.misc + 4));
+    GR_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(cloud_cell_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, D, g.B, g.cell, g.count, g.misc);
   GR_LAUNCH_CHECK();
   const int rc = exclusive_scan_i32(g.count, g.count, cells + 1, 1, cells + 1, g.scan_ws, nullptr, stream);
   if (rc != GR_OK) return rc;
   hipLaunchKernelGGL(cloud_scatter_kernel, dim3(sblocks), dim3(THREADS), 0, stream, support, ns, g.cell, g.count, g.cursor,
-                     g.sorted, (int32_t*)nullptr);
+                     g.sorted, g.sorted_cell);
   GR_LAUNCH_CHECK();
   return GR_OK;
 }

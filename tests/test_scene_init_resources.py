@@ -9,10 +9,8 @@ from gaussreg_amd import scene_init  # noqa: F401  (the module whose kernels the
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 # LDS bytes per workgroup, VGPRs, and the compiler's waves per SIMD
-KERNELS = (("gs_knn_boundaries_kernel", {"LDS Size": 16384, "VGPRs": 22, "Occupancy": 8}),
-           ("gs_knn_count_kernel", {"LDS Size": 1536, "VGPRs": 10, "Occupancy": 8}),
-           ("gs_knn_scatter_kernel", {"LDS Size": 0, "VGPRs": 12, "Occupancy": 8}),
-           ("gs_knn_query_kernel<1>", {"LDS Size": 0, "VGPRs": 40, "Occupancy": 8}),
+# (the grid is built by the kernels of cloud_nn.hip, whose figures tests/test_cloud_nn_resources.py asserts)
+KERNELS = (("gs_knn_query_kernel<1>", {"LDS Size": 0, "VGPRs": 40, "Occupancy": 8}),
            ("gs_knn_query_kernel<3>", {"LDS Size": 0, "VGPRs": 46, "Occupancy": 8}),
            ("gs_knn_query_kernel<5>", {"LDS Size": 0, "VGPRs": 55, "Occupancy": 8}),
            ("gs_knn_query_kernel<8>", {"LDS Size": 0, "VGPRs": 68, "Occupancy": 7}))
