@@ -17,6 +17,7 @@ from gaussreg_amd import synthetic  # noqa: E402
 from oracle import capi  # noqa: E402
 
 TILE, STEP = 16, 64
+WAVE_STEPS = 8  # steps of a wave of the 256-thread scatter: a quarter of a 2 048-Gaussian chunk
 
 
 def device_rects(pp, W, H):
@@ -99,6 +100,18 @@ def main(P=1_000_000, W=640, H=480, *cams):
           % tuple(100.0 * sides[1:6] / max(n_steps, 1)))
     print("rounds per step   now (2 / 4 / 8 squared) %.2f   exact square %.2f   exact rectangle %.2f   lower bound %.2f"
           % tuple(acc[k] / max(n_steps, 1) for k in ("now", "square", "rect", "bound")))
+    # Phase A of the 256-thread scatter no longer walks: per step four corner adds into the wave's difference grid, and per
+    # wave (WAVE_STEPS steps) the two prefix passes over its cursor row -- a read and a write per grid row and lane round down
+    # the columns, the same per word (cell, for an odd gx) along the rows (+ a pass over the words that splits the halves,
+    # for an odd gx).  The walk of phase A cost the rounds of the exact rectangle; phase C still does.
+    gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
+    up = lambda a, b: (a + b - 1) // b  # noqa: E731
+    if gx % 2 == 0:
+        prefix = 2 * gy * up(gx // 2, STEP) + 2 * (gx // 2) * up(gy, STEP)
+    else:
+        prefix = 2 * up((gx * gy + 1) // 2, STEP) + 2 * gy * up(gx, STEP) + 2 * gx * up(gy, STEP)
+    print("phase A, LDS instructions per step   walk (exact rectangle) %.2f   grid: 4 corner adds + %d prefix / %d steps = %.2f"
+          "   (%d x %d tiles)" % (acc["rect"] / max(n_steps, 1), prefix, WAVE_STEPS, 4 + prefix / WAVE_STEPS, gx, gy))
 
 
 if __name__ == "__main__":
