@@ -3,6 +3,7 @@
 #pragma once
 
 #include "common.hpp"
+#include "raster_plan.hpp"  // BIN_T, BIN_CHUNK and the other constants the frame plan needs
 
 namespace gr {
 namespace {
@@ -179,9 +180,6 @@ struct Geom {
   int32_t* scan_ws;
   size_t bytes;
 };
-
-constexpr int BIN_T = 256;                          // threads per binning workgroup (4 waves)
-constexpr int BIN_CHUNK = 2048;                     // depth-ordered Gaussians per chunk (count: a workgroup, scatter: a wave)
 
 Geom carve_geom(void* p, int64_t P, int V, int64_t tiles) {
   Geom g;

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include <atomic>
+#include <optional>
 
 #include "raster_shared.hpp"
 
@@ -28,6 +29,8 @@ namespace gr {
 namespace {
 
 static_assert(TILE == RASTER_TILE, "get_rect / rect_decode (common.hpp) are written for this tile size");
+static_assert(TILE == PLAN_TILE && WAVE == PLAN_WAVE && SCAN_SINGLE_ROW == PLAN_SCAN_SINGLE_ROW && MAX_VIEWS == PLAN_MAX_VIEWS,
+              "raster_plan.hpp states these values for itself");
 
 
 // ------------------------------------------------------------------------------------ preprocess
@@ -38,6 +41,7 @@ static_assert(TILE == RASTER_TILE, "get_rect / rect_decode (common.hpp) are writ
 // while depth < 8192): 27 bits sort in three 9-bit passes.  A depth >= 8192 raises a flag and the call re-sorts on the
 // full 32 depth bits (slow path, never taken by sane scenes).
 constexpr int KEY_DEPTH_BITS = 27;
+static_assert(KEY_DEPTH_BITS == PLAN_KEY_DEPTH_BITS, "raster_plan.hpp states this value for itself");
 constexpr uint32_t KEY_DEPTH_BASE = 0x3E000000u;  // bits of 0.125f
 
 __device__ __forceinline__ uint32_t pack_rect(const int* rmin, const int* rmax) {
@@ -138,13 +142,7 @@ __device__ __forceinline__ bool bin_block(int V, int nchunk, int& v, int& c) {
   return true;
 }
 inline int bin_grid(int V, int nchunk) { return V >= 8 ? 8 * ((V + 7) / 8) * nchunk : V * nchunk; }
-// a few views per call (short chunk rows): tile_count_kernel + seg_scan_kernel<true> write seg_off; otherwise only the
-// chunk totals are counted and scanned, and the scatter writes seg_off itself
-inline bool bin_scans_self(int nchunk, int V) { return !(nchunk <= SCAN_SINGLE_ROW && V <= 4); }
-// many views: resident scatter workgroups per CU that the LDS staging block is sized for (measured at 1 M Gaussians,
-// 640 x 480, 32 views: 4 / 5 / 6 / 8 -> 308 / 306 / 278 / 370 us; at 6, 2 % of the chunks take the direct path)
-constexpr int SCATTER_WGS = 6;
-constexpr int WIDE_T = 1024;  // threads per scatter workgroup for a few views per call
+// (which launches count for which frame, the scatter's workgroup size and its LDS: raster_plan.hpp)
 
 // n mod d for n < 256, 1 <= d <= 8, exact: with m = floor(2^15 / d) + 1 the error m d - 2^15 is at most d, and
 // 255 * 8 < 2^15, so (n m) >> 15 = floor(n / d).  The eight 16-bit multipliers sit in two literals (d wave-uniform:
@@ -360,7 +358,7 @@ __global__ __launch_bounds__(256) void seg_scan_kernel(int V, int tiles, int nch
 //   SEG_SELF_SCAN  (many views per call): chunk_total_kernel + exclusive_scan_i32 left the raw totals, the chunk bases
 //                  inside every view (chunk_total + V * nchunk) and the view totals
 // In both SELF modes the workgroup scans the tile counts it has to build anyway and WRITES its row of seg_off for the blend.
-constexpr int SEG_READ = 0, SEG_SELF_RAW = 1, SEG_SELF_SCAN = 2;
+// (the constants: raster_plan.hpp)
 struct SelfSeg {
   const int32_t* chunk_total;
   int32_t* totals;
@@ -1351,37 +1349,194 @@ extern "C" size_t gr_raster_bin_bytes(int64_t total_rendered, int width, int hei
   return carve_bin(nullptr, total_rendered, tiles_of(width, height) * num_views).bytes;
 }
 
-// How the counts of a deferred (speculative) frame reach the host:
-//   mail    the counting kernel itself stores them into host-mapped pinned memory and stamps them with `seq`; the host polls
-//           the stamps (a few views per call on the self-scanning path: nothing but kernels sits in the stream)
-//   event   a device-to-host copy on a side stream, followed by `ev`
+// What travels between the two halves of a deferred (speculative) frame: its plan (raster_plan.hpp -- which launches count,
+// whether the counts come by mail or behind the event, what the scatter reads) and what the wait for the counts needs.
 struct Deferred {
-  hipEvent_t ev;
-  volatile int32_t* mail;  // [V] totals, [V] chunk maxima, [1] far word, [V] stamps
+  hipEvent_t ev;           // Transport::Event: follows the copy of the counts on the side stream
+  volatile int32_t* mail;  // Transport::Mail: the words the counting kernel posts (null: this thread has no mailbox)
   int seq;                 // this frame's stamp (never 0)
-  int far_seq;             // the far word equals this value iff a depth overflowed the compact keys (and its negative iff a
-                           // bucket of the four-launch depth sort did not fit: the order is then not valid either)
-  bool by_mail;            // out: which of the two ways this frame took
-  bool bucket_sort;        // in: take the four-launch depth sort
-  bool self_seg;           // out: the depth sort left the chunk totals and nothing else was launched -- the scatter of this
-                           // frame scans its own segments and mails the counts (tile_scatter_kernel SEG_SELF_RAW)
+  int far_seq;             // what a far depth leaves in the far word (a bucket overflow: its negative)
+  FramePlan plan;
 };
 
-// defer_ev != nullptr: everything is enqueued, the read-back of the counts is followed by this event instead of a stream
-// synchronise, and h_num_rendered is NOT filled -- the caller waits for the event and calls preprocess_collect().
-static int preprocess_impl(int64_t P, int M, const float* means3D, const float* shs,
-                           const float* colors_precomp, const float* opacities,
-                           const float* scales, const float* rotations,
-                           const float* cov3D_precomp, const gr_raster_view* h_views,
-                           int num_views, int32_t* radii, void* geom, size_t geom_bytes,
-                           int64_t* h_num_rendered, hipStream_t stream, Deferred* defer_ev) {
+// the caller's arrays of one preprocess call
+struct SceneArgs {
+  int64_t P;
+  int M;
+  const float *means3D, *shs, *colors_precomp, *opacities, *scales, *rotations, *cov3D_precomp;
+  int32_t* radii;
+};
+
+using PreprocessFn = decltype(&preprocess_kernel<false, false, false, false>);
+static PreprocessFn preprocess_fn(bool has_sh, bool has_cov, bool sh16, PreprocessKind kind) {
+  // rows (HAS_SH, HAS_COV, SH16); columns: PreprocessKind Late (a plan asks for it on SH16 rows only), Many, Plain
+  static const PreprocessFn table[6][3] = {
+      {preprocess_kernel<true, true, true, true>, preprocess_many_kernel<true, true, true>, preprocess_kernel<true, true, true, false>},
+      {preprocess_kernel<true, true, false, false>, preprocess_many_kernel<true, true, false>, preprocess_kernel<true, true, false, false>},
+      {preprocess_kernel<true, false, true, true>, preprocess_many_kernel<true, false, true>, preprocess_kernel<true, false, true, false>},
+      {preprocess_kernel<true, false, false, false>, preprocess_many_kernel<true, false, false>, preprocess_kernel<true, false, false, false>},
+      {preprocess_kernel<false, true, false, false>, preprocess_many_kernel<false, true, false>, preprocess_kernel<false, true, false, false>},
+      {preprocess_kernel<false, false, false, false>, preprocess_many_kernel<false, false, false>, preprocess_kernel<false, false, false, false>}};
+  const int row = has_sh ? (has_cov ? 0 : 2) + (sh16 ? 0 : 1) : has_cov ? 4 : 5;
+  return table[row][kind == PreprocessKind::Late ? 0 : kind == PreprocessKind::Many ? 1 : 2];
+}
+
+static int launch_preprocess(const FramePlan& plan, const SceneArgs& a, int D, int W, int H, const Geom& g, const DevView& cam1,
+                             int far_seq, hipStream_t stream) {
+  const dim3 blk(256), grd((unsigned)((a.P + 255) / 256));
+  {
+    KernelTimer timer("raster_preprocess", stream);
+    hipLaunchKernelGGL(preprocess_fn(a.shs != nullptr, a.cov3D_precomp != nullptr, plan.sh16, plan.preprocess), grd, blk, 0, stream,
+                       (int)a.P, D, a.M, plan.V, g.views, a.means3D, a.shs, a.colors_precomp, a.opacities, a.scales, a.rotations,
+                       a.cov3D_precomp, W, H, a.radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * plan.V, cam1, far_seq,
+                       plan.msd ? g.key_mm : nullptr);
+  }
+  GR_LAUNCH_CHECK();
+  return GR_OK;
+}
+
+// The counts on their way to the host.  Sync: they are in `tot` on return.  Event: a device-to-host copy on a SIDE stream,
+// so the scatter and the blend that follow on `stream` do not queue behind it (it held the stream for 4.2 us + a 5.7 us
+// hand-over gap, profiles/r03_single_view_timeline.txt).  Mail: nothing to do, the counting kernel mails them itself.
+static int send_counts(const FramePlan& plan, const Geom& g, int32_t* tot, hipStream_t stream, const Deferred* d) {
+  if (plan.transport == Transport::Mail) return GR_OK;
+  const int V = plan.V;
+  hipStream_t via = stream;
+  if (plan.transport == Transport::Event) {
+    static thread_local hipStream_t side = nullptr;
+    static thread_local hipEvent_t counted = nullptr;
+    if (side == nullptr) GR_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
+    if (counted == nullptr) GR_HIP(hipEventCreateWithFlags(&counted, hipEventDisableTiming));
+    GR_HIP(hipEventRecord(counted, stream));
+    GR_HIP(hipStreamWaitEvent(side, counted, 0));
+    via = side;
+  }
+  GR_HIP(hipMemcpyAsync(tot, g.totals, sizeof(int32_t) * (2 * V + 1), hipMemcpyDeviceToHost, via));
+  if (!plan.short_rows) GR_HIP(hipMemcpyAsync(tot + 2 * V + 1, g.chunk_max, sizeof(int32_t), hipMemcpyDeviceToHost, via));
+  if (plan.transport == Transport::Event)
+    GR_HIP(hipEventRecord(d->ev, via));
+  else
+    GR_HIP(hipStreamSynchronize(stream));
+  return GR_OK;
+}
+
+// Every view's visible Gaussians in depth order (ties: Gaussian id): ids -> order_b, rectangles -> rects.  Then the count
+// launches of plan.route (DESIGN.md 3.3 has the table), and the counts on their way by plan.transport.
+// d: the deferred frame this is the first half of (null: a plain frame).
+static int sort_and_count(const FramePlan& plan, const Geom& g, int64_t P, int32_t* tot, hipStream_t stream, const Deferred* d) {
+  const int V = plan.V, nchunk = plan.nchunk, tiles = plan.tiles;
+  {
+    KernelTimer timer("raster_depth_sort", stream);
+    // a bucket that outgrows LDS raises the far word: bit 1 on a plain frame (which reads the counts itself and redoes the
+    // ordering in place), the negative stamp on a deferred one (whose caller then takes the plain path)
+    const DepthSortTotals ct{g.chunk_total, BIN_CHUNK, nchunk, g.rec, plan.gx, plan.gy};
+    int rc = depth_sort_views(g.dfield, g.rect_raw, g.keys_a, g.keys_b, g.order_b, g.rects, g.nvis, P, V, plan.key_bits,
+                              g.ds_table, g.ds_table_bytes, stream, plan.msd ? g.key_mm : nullptr,
+                              V > 4 ? (int)((P + 255) / 256) * (256 / WAVE) : (int)((P + 255) / 256), g.totals + 2 * V,
+                              d != nullptr ? -d->far_seq : 2,
+                              plan.route == CountRoute::SelfRaw || plan.totals_sorted ? &ct : nullptr);
+    if (rc != GR_OK) return rc;
+  }
+  if (plan.route == CountRoute::SelfRaw) return GR_OK;
+  {
+    KernelTimer timer("raster_bin", stream);
+    // chunk bases inside each view (+ the per-view totals R_v and the largest chunk total, which sizes the scatter's
+    // staging block), and every chunk's per-tile segment starts
+    if (plan.route == CountRoute::CountScan) {
+      if (tiles * sizeof(unsigned int) > 64 * 1024)
+        GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_count_kernel),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+      hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)bin_grid(V, nchunk)), dim3(BIN_T), tiles * sizeof(unsigned int),
+                         stream, (int)P, V, plan.gx, plan.gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_cnt,
+                         g.chunk_total);
+      const bool mail = plan.transport == Transport::Mail;
+      hipLaunchKernelGGL(seg_scan_kernel<true>, dim3((unsigned)(V * nchunk)), dim3(256), 0, stream, V, tiles, nchunk,
+                         g.chunk_cnt, g.chunk_total, g.totals, g.seg_off, mail ? const_cast<int32_t*>(d->mail) : nullptr,
+                         mail ? d->seq : 0);
+      GR_LAUNCH_CHECK();
+    } else {
+      if (!plan.totals_sorted)
+        hipLaunchKernelGGL(chunk_total_kernel, dim3((unsigned)bin_grid(V, nchunk)), dim3(BIN_T), 0, stream, (int)P, V, plan.gx,
+                           plan.gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_total);
+      if (!plan.short_rows)
+        hipLaunchKernelGGL(chunk_max_kernel, dim3(1), dim3(1024), 0, stream, V * nchunk, g.chunk_total, g.chunk_max);
+      GR_LAUNCH_CHECK();
+      int rc = exclusive_scan_i32(g.chunk_total, g.chunk_total + (int64_t)V * nchunk, nchunk, V, nchunk, g.scan_ws, g.totals,
+                                  stream, nullptr, plan.short_rows ? g.totals + V : nullptr);
+      if (rc != GR_OK) return rc;
+    }
+  }
+  return send_counts(plan, g, tot, stream, d);
+}
+
+// first frames of the process: is every view really in (depth, id) order?  1: it was not, and the process now ranks by ballot
+static int check_depth_order(int64_t P, int V, const Geom& g, hipStream_t stream) {
+  if (!verify_this_frame()) return GR_OK;
+  int h_bad = 0;
+  int rc = device_check(stream, [&](int* d_bad) {
+    hipLaunchKernelGGL(verify_depth_order_kernel, dim3((unsigned)std::min<int64_t>((P + 255) / 256, 4096), V), dim3(256), 0,
+                       stream, (int)P, V, g.nvis, g.dfield, g.order_b, reinterpret_cast<int32_t*>(g.keys_a), d_bad);
+  }, &h_bad);
+  if (rc != GR_OK) return rc;
+  if (h_bad != 0 && lds_atomics_lane_ordered_state() == 1) {
+    lds_order_demote();  // the lane-order property did not hold under load: explicit ranking from now on
+    return 1;
+  }
+  GR_REQUIRE(h_bad == 0, "depth sort produced an unsorted order (internal error)");
+  return GR_OK;
+}
+
+// A plain frame after its first sort_and_count: the redo rules, then the counts -> h_num_rendered.
+static int redo_and_report(FramePlan plan, const SceneArgs& a, const Geom& g, int32_t* tot, hipStream_t stream,
+                           int64_t* h_num_rendered) {
+  const int V = plan.V;
+  Counts c = decode_counts(tot, V, plan.short_rows, Transport::Sync, 0);
+  int rc;
+  if (c.bucket_overflow) {  // a bucket of the bucket depth sort overflowed: three passes, now and for a while
+    bucket_sort_overflowed();
+    GR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.totals + 2 * V), c.far_depth ? 1 : 0, 1, stream));
+    plan = plan.without_buckets();
+    rc = sort_and_count(plan, g, a.P, tot, stream, nullptr);
+    if (rc != GR_OK) return rc;
+    c = decode_counts(tot, V, plan.short_rows, Transport::Sync, 0);
+  }
+  if (c.far_depth) {  // some depth >= 8192: redo the ordering with full-width keys
+    hipLaunchKernelGGL(full_keys_kernel, dim3((unsigned)((a.P * V + 255) / 256)), dim3(256), 0, stream, a.P * V, g.rec, a.radii,
+                       g.dfield);
+    GR_LAUNCH_CHECK();
+    plan = plan.with_full_keys();
+    rc = sort_and_count(plan, g, a.P, tot, stream, nullptr);
+    if (rc != GR_OK) return rc;
+    c = decode_counts(tot, V, plan.short_rows, Transport::Sync, 0);
+  }
+  rc = check_depth_order(a.P, V, g, stream);
+  if (rc == 1) {
+    plan = plan.without_buckets();
+    rc = sort_and_count(plan, g, a.P, tot, stream, nullptr);
+    if (rc != GR_OK) return rc;
+    c = decode_counts(tot, V, plan.short_rows, Transport::Sync, 0);
+    rc = check_depth_order(a.P, V, g, stream);
+    if (rc == 1) rc = GR_OK;
+  }
+  if (rc != GR_OK) return rc;
+  for (int v = 0; v < V; ++v) h_num_rendered[v] = c.totals[v];
+  h_num_rendered[V] = c.chunk_max;  // sizes the scatter's LDS staging block in gr_raster_render
+  return GR_OK;
+}
+
+// defer != nullptr: everything is enqueued, the counts are on their way as defer->plan.transport says instead of behind a
+// stream synchronise, and h_num_rendered is NOT filled -- the caller calls preprocess_collect().  bucket_sort: whether that
+// frame takes the bucket depth sort (a plain call asks the cooldown itself).
+static int preprocess_impl(const SceneArgs& a, const gr_raster_view* h_views, int num_views, void* geom, size_t geom_bytes,
+                           int64_t* h_num_rendered, hipStream_t stream, Deferred* defer, bool bucket_sort) {
   int rc = check_views(h_views, num_views);
   if (rc != GR_OK) return rc;
   GR_REQUIRE(h_num_rendered != nullptr, "h_num_rendered is null");
   for (int v = 0; v <= num_views; ++v) h_num_rendered[v] = 0;
-  GR_REQUIRE(P >= 0 && P < (1ll << 31) - 1, "P out of range");
-  if (P == 0) {  // nothing to project, but the render call still needs the camera table (background)
-    Geom g0 = carve_geom(geom, 0, num_views, tiles_of(h_views[0].image_width, h_views[0].image_height));
+  GR_REQUIRE(a.P >= 0 && a.P < (1ll << 31) - 1, "P out of range");
+  const int W = h_views[0].image_width, H = h_views[0].image_height;
+  if (a.P == 0) {  // nothing to project, but the render call still needs the camera table (background)
+    Geom g0 = carve_geom(geom, 0, num_views, tiles_of(W, H));
     if (!geom || geom_bytes < g0.bytes) {
       set_error("raster geometry buffer too small: need %zu bytes, got %zu", g0.bytes, geom_bytes);
       return GR_ERR_WORKSPACE;
@@ -1391,206 +1546,48 @@ static int preprocess_impl(int64_t P, int M, const float* means3D, const float* 
     GR_HIP(hipStreamSynchronize(stream));
     return GR_OK;
   }
-  GR_REQUIRE(means3D && opacities && radii, "means3D / opacities / radii must be non-null");
-  GR_REQUIRE((shs != nullptr) != (colors_precomp != nullptr),
+  GR_REQUIRE(a.means3D && a.opacities && a.radii, "means3D / opacities / radii must be non-null");
+  GR_REQUIRE((a.shs != nullptr) != (a.colors_precomp != nullptr),
              "Please provide excatly one of either SHs or precomputed colors!");
-  GR_REQUIRE(((scales != nullptr && rotations != nullptr) != (cov3D_precomp != nullptr)) &&
-                 ((scales != nullptr) == (rotations != nullptr)),
+  GR_REQUIRE(((a.scales != nullptr && a.rotations != nullptr) != (a.cov3D_precomp != nullptr)) &&
+                 ((a.scales != nullptr) == (a.rotations != nullptr)),
              "Please provide exactly one of either scale/rotation pair or precomputed 3D covariance!");
   const int D = h_views[0].sh_degree;
-  if (shs) GR_REQUIRE(M >= (D + 1) * (D + 1), "shs has %d coefficients, sh_degree %d needs %d", M, D, (D + 1) * (D + 1));
-  const int W = h_views[0].image_width, H = h_views[0].image_height;
+  if (a.shs) GR_REQUIRE(a.M >= (D + 1) * (D + 1), "shs has %d coefficients, sh_degree %d needs %d", a.M, D, (D + 1) * (D + 1));
   const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
-  const int tiles = gx * gy;
   GR_REQUIRE(gx <= 255 && gy <= 255, "image too large: at most 255 x 255 tiles of 16 px (got %d x %d)", gx, gy);
-  const size_t bin_lds = (size_t)(BIN_T / WAVE) * tiles * sizeof(unsigned int);
+  const size_t bin_lds = (size_t)(BIN_T / WAVE) * gx * gy * sizeof(unsigned int);
   GR_REQUIRE(bin_lds <= 156 * 1024, "image too large: the per-wave tile cursors (%zu bytes) do not fit in LDS", bin_lds);
-  Geom g = carve_geom(geom, P, num_views, tiles);
+  const Geom g = carve_geom(geom, a.P, num_views, gx * gy);
   if (!geom || geom_bytes < g.bytes) {
     set_error("raster geometry buffer too small: need %zu bytes, got %zu", g.bytes, geom_bytes);
     return GR_ERR_WORKSPACE;
   }
-  const dim3 blk(256), grd((unsigned)((P + 255) / 256));
-  const bool sh16 = shs != nullptr && M == 16 && (reinterpret_cast<uintptr_t>(shs) % 16 == 0);
-  // one camera, deferred frame: the camera rides in the kernel arguments of the preprocess kernel and a far depth stores
-  // this call's stamp into the flag word -- no upload, no clear in front of the frame
-  // (only when the counts will leave through the mailbox, i.e. the chunk rows are short enough for the self-scanning count
-  // launch: the event path below reads the far flag as "non-zero", which needs the upload's clear)
-  const bool cam_in_args = sh16 && num_views == 1 && defer_ev != nullptr && defer_ev->mail != nullptr &&
-                           (P + BIN_CHUNK - 1) / BIN_CHUNK <= SCAN_SINGLE_ROW;
+  const bool sh16 = a.shs != nullptr && a.M == 16 && (reinterpret_cast<uintptr_t>(a.shs) % 16 == 0);
+  const FramePlan plan = FramePlan::make(
+      a.P, num_views, W, H, sh16, defer != nullptr, defer != nullptr && defer->mail != nullptr,
+      defer != nullptr ? bucket_sort : bucket_sort_allowed(depth_sort_msd_possible(a.P, num_views, KEY_DEPTH_BITS)));
   DevView cam1;
   memset(&cam1, 0, sizeof(cam1));
+  if (plan.preprocess == PreprocessKind::Late) fill_view(cam1, h_views[0]);  // that kernel always reads the camera from its arguments
   int far_seq = 1;
-  if (sh16 && num_views == 1) fill_view(cam1, h_views[0]);  // the one-view kernel variant always reads the camera from its arguments
-  if (cam_in_args) {
-    far_seq = defer_ev->seq;
+  if (plan.cam_in_args) {
+    far_seq = defer->seq;
   } else {
     rc = upload_views(h_views, num_views, g.totals + 2 * num_views, stream);  // cameras + the cleared depth-overflow flag
     if (rc != GR_OK) return rc;
   }
-  if (defer_ev != nullptr) defer_ev->far_seq = far_seq;
-  // a deferred frame of a few views: the four-launch depth sort (a bucket that outgrows LDS raises the far word with the
-  // sign flipped; the caller then takes the plain path, which always sorts in three passes)
-  // (a plain call reads the counts itself: bit 1 of the far word says "overflow" there and the ordering is redone in place)
-  // more than four views per call (always a plain call): the same sort, fed by per-wave key ranges (preprocess_many_kernel)
-  const bool msd_possible = depth_sort_msd_possible(P, num_views, KEY_DEPTH_BITS);
-  const bool msd = msd_possible && (defer_ev != nullptr ? defer_ev->bucket_sort : bucket_sort_allowed(true));
-  int2* const mm_out = msd ? g.key_mm : nullptr;
-#define GR_PRE(SH, COV, S16)                                                                       \
-  if (S16 && num_views == 1)                                                                       \
-    hipLaunchKernelGGL((preprocess_kernel<SH, COV, S16, S16>), grd, blk, 0, stream, (int)P, D, M, num_views, \
-                       g.views, means3D, shs, colors_precomp, opacities, scales, rotations,        \
-                       cov3D_precomp, W, H, radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * num_views, cam1, far_seq, \
-                       mm_out);                                                                    \
-  else if (msd && num_views > 4)                                                                   \
-    hipLaunchKernelGGL((preprocess_many_kernel<SH, COV, S16>), grd, blk, 0, stream, (int)P, D, M, num_views, \
-                       g.views, means3D, shs, colors_precomp, opacities, scales, rotations,        \
-                       cov3D_precomp, W, H, radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * num_views, cam1, far_seq, \
-                       mm_out);                                                                    \
-  else                                                                                             \
-  hipLaunchKernelGGL((preprocess_kernel<SH, COV, S16, false>), grd, blk, 0, stream, (int)P, D, M, num_views, \
-                     g.views, means3D, shs, colors_precomp, opacities, scales, rotations,          \
-                     cov3D_precomp, W, H, radii, g.rec, g.dfield, g.rect_raw, g.totals + 2 * num_views, cam1, far_seq, \
-                     mm_out)
-  auto run_preprocess = [&]() {
-    KernelTimer timer("raster_preprocess", stream);
-    if (shs && cov3D_precomp) { if (sh16) GR_PRE(true, true, true); else GR_PRE(true, true, false); }
-    else if (shs) { if (sh16) GR_PRE(true, false, true); else GR_PRE(true, false, false); }
-    else if (cov3D_precomp) GR_PRE(false, true, false);
-    else GR_PRE(false, false, false);
-  };
-  run_preprocess();
-  GR_LAUNCH_CHECK();
-  int32_t* tot = static_cast<int32_t*>(pinned_scratch(1, sizeof(int32_t) * (2 * num_views + 2)));  // totals, far flag, chunk maxima
+  if (defer != nullptr) {
+    defer->far_seq = far_seq;
+    defer->plan = plan;
+  }
+  rc = launch_preprocess(plan, a, D, W, H, g, cam1, far_seq, stream);
+  if (rc != GR_OK) return rc;
+  int32_t* tot = static_cast<int32_t*>(pinned_scratch(1, sizeof(int32_t) * (2 * num_views + 2)));
   GR_REQUIRE(tot != nullptr, "pinned read-back buffer could not be allocated");
-  const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
-  int32_t h_chunk_max = 0;
-  auto sort_and_count = [&](int key_bits, bool buckets = true) -> int {
-    bool totals_sorted = false;
-    {
-      KernelTimer timer("raster_depth_sort", stream);
-      // visible Gaussians of every view in depth order (ties: Gaussian id): ids -> order_b, rectangles -> rects
-      const bool msd_now = msd && buckets && key_bits == KEY_DEPTH_BITS;
-      // ... and with the mailbox: no count / scan launch either, the scatter does both (its SEG_SELF_RAW variant)
-      const bool self_seg = msd_now && defer_ev != nullptr && defer_ev->mail != nullptr && nchunk <= SCAN_SINGLE_ROW &&
-                            num_views <= 4;
-      // many views: the bucket launch adds up the chunk totals as well -- the binning starts at its scan
-      totals_sorted = msd_now && num_views > 4;
-      const DepthSortTotals ct{g.chunk_total, BIN_CHUNK, nchunk, g.rec, gx, gy};
-      int rcs = depth_sort_views(g.dfield, g.rect_raw, g.keys_a, g.keys_b, g.order_b, g.rects, g.nvis, P, num_views, key_bits,
-                                 g.ds_table, g.ds_table_bytes, stream, msd_now ? g.key_mm : nullptr,
-                                 num_views > 4 ? (int)((P + 255) / 256) * (256 / WAVE) : (int)((P + 255) / 256),
-                                 g.totals + 2 * num_views, defer_ev != nullptr ? -far_seq : 2,
-                                 self_seg || totals_sorted ? &ct : nullptr);
-      if (rcs != GR_OK) return rcs;
-      if (self_seg) {
-        defer_ev->by_mail = true;
-        defer_ev->self_seg = true;
-        return GR_OK;
-      }
-    }
-    {
-      KernelTimer timer("raster_bin", stream);
-      // chunk bases inside each view (+ the per-view totals R_v and the largest chunk total, which sizes the scatter's
-      // staging block), and every chunk's per-tile segment starts: by the count / scan launches for a few views, by the
-      // scatter itself otherwise
-      const bool short_rows = nchunk <= SCAN_SINGLE_ROW;  // one launch does scan, totals and maxima
-      if (!bin_scans_self(nchunk, num_views)) {  // ... or none at all: seg_scan_kernel<true> sums what it needs
-        if (tiles * sizeof(unsigned int) > 64 * 1024)
-          GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(tile_count_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T),
-                           tiles * sizeof(unsigned int), stream, (int)P, num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b,
-                           g.rec, g.chunk_cnt, g.chunk_total);
-        const bool by_mail = defer_ev != nullptr && defer_ev->mail != nullptr;
-        hipLaunchKernelGGL(seg_scan_kernel<true>, dim3((unsigned)(num_views * nchunk)), blk, 0, stream, num_views, tiles, nchunk,
-                           g.chunk_cnt, g.chunk_total, g.totals, g.seg_off, by_mail ? const_cast<int32_t*>(defer_ev->mail) : nullptr,
-                           by_mail ? defer_ev->seq : 0);
-        if (by_mail) defer_ev->by_mail = true;
-        GR_LAUNCH_CHECK();
-      } else {
-        // only the chunk totals: the scatter (SEG_SELF_SCAN) counts the tiles of its chunk and writes its row of seg_off
-        if (!totals_sorted)
-          hipLaunchKernelGGL(chunk_total_kernel, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(BIN_T), 0, stream, (int)P,
-                             num_views, gx, gy, nchunk, g.nvis, g.rects, g.order_b, g.rec, g.chunk_total);
-        if (!short_rows)
-          hipLaunchKernelGGL(chunk_max_kernel, dim3(1), dim3(1024), 0, stream, num_views * nchunk, g.chunk_total, g.chunk_max);
-        GR_LAUNCH_CHECK();
-        int rcs = exclusive_scan_i32(g.chunk_total, g.chunk_total + (int64_t)num_views * nchunk, nchunk, num_views, nchunk,
-                                     g.scan_ws, g.totals, stream, nullptr, short_rows ? g.totals + num_views : nullptr);
-        if (rcs != GR_OK) return rcs;
-      }
-    }
-    const bool short_rows = nchunk <= SCAN_SINGLE_ROW;
-    // tot: [V] totals, [V] per-view chunk maxima (short rows), [1] depth-overflow flag, [1] chunk maximum (long rows)
-    if (defer_ev != nullptr) {
-      if (defer_ev->by_mail) return GR_OK;  // the counting kernel mails the counts itself
-      // else: a device-to-host copy on a SIDE stream, so the scatter and the blend that follow on `stream` do not queue
-      // behind it (it held the stream for 4.2 us + a 5.7 us hand-over gap, profiles/r03_single_view_timeline.txt)
-      static thread_local hipStream_t side = nullptr;
-      static thread_local hipEvent_t counted = nullptr;
-      if (side == nullptr) GR_HIP(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-      if (counted == nullptr) GR_HIP(hipEventCreateWithFlags(&counted, hipEventDisableTiming));
-      GR_HIP(hipEventRecord(counted, stream));
-      GR_HIP(hipStreamWaitEvent(side, counted, 0));
-      GR_HIP(hipMemcpyAsync(tot, g.totals, sizeof(int32_t) * (2 * num_views + 1), hipMemcpyDeviceToHost, side));
-      if (!short_rows)
-        GR_HIP(hipMemcpyAsync(tot + 2 * num_views + 1, g.chunk_max, sizeof(int32_t), hipMemcpyDeviceToHost, side));
-      GR_HIP(hipEventRecord(defer_ev->ev, side));
-      return GR_OK;
-    }
-    GR_HIP(hipMemcpyAsync(tot, g.totals, sizeof(int32_t) * (2 * num_views + 1), hipMemcpyDeviceToHost, stream));
-    if (!short_rows)
-      GR_HIP(hipMemcpyAsync(tot + 2 * num_views + 1, g.chunk_max, sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    GR_HIP(hipStreamSynchronize(stream));
-    h_chunk_max = short_rows ? tot[num_views] : tot[2 * num_views + 1];
-    if (short_rows)
-      for (int v = 1; v < num_views; ++v) h_chunk_max = std::max(h_chunk_max, tot[num_views + v]);
-    return GR_OK;
-  };
-  rc = sort_and_count(KEY_DEPTH_BITS);
-  if (rc != GR_OK) return rc;
-  if (defer_ev != nullptr) return GR_OK;
-  auto check_depth_order = [&]() -> int {  // first frames of the process: is every view really in (depth, id) order?
-    if (!verify_this_frame()) return GR_OK;
-    int h_bad = 0;
-    int rcv = device_check(stream, [&](int* d_bad) {
-      hipLaunchKernelGGL(verify_depth_order_kernel, dim3((unsigned)std::min<int64_t>((P + 255) / 256, 4096), num_views), blk, 0,
-                         stream, (int)P, num_views, g.nvis, g.dfield, g.order_b, reinterpret_cast<int32_t*>(g.keys_a), d_bad);
-    }, &h_bad);
-    if (rcv != GR_OK) return rcv;
-    if (h_bad != 0 && lds_atomics_lane_ordered_state() == 1) {
-      lds_order_demote();  // the lane-order property did not hold under load: explicit ranking from now on
-      return 1;
-    }
-    GR_REQUIRE(h_bad == 0, "depth sort produced an unsorted order (internal error)");
-    return GR_OK;
-  };
-  if (tot[2 * num_views] & 2) {  // a bucket of the four-launch sort overflowed: three passes, now and for a while
-    bucket_sort_overflowed();
-    GR_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.totals + 2 * num_views), tot[2 * num_views] & 1, 1, stream));
-    rc = sort_and_count(KEY_DEPTH_BITS, false);
-    if (rc != GR_OK) return rc;
-  }
-  if (tot[2 * num_views] != 0) {  // some depth >= 8192: redo the ordering with full-width keys
-    hipLaunchKernelGGL(full_keys_kernel, dim3((unsigned)((P * num_views + 255) / 256)), blk, 0, stream, P * num_views,
-                       g.rec, radii, g.dfield);
-    GR_LAUNCH_CHECK();
-    rc = sort_and_count(32);
-    if (rc != GR_OK) return rc;
-  }
-  rc = check_depth_order();
-  if (rc == 1) {
-    rc = sort_and_count(tot[2 * num_views] != 0 ? 32 : KEY_DEPTH_BITS, false);
-    if (rc != GR_OK) return rc;
-    rc = check_depth_order();
-    if (rc == 1) rc = GR_OK;
-  }
-  if (rc != GR_OK) return rc;
-#undef GR_PRE
-  for (int v = 0; v < num_views; ++v) h_num_rendered[v] = tot[v];
-  h_num_rendered[num_views] = h_chunk_max;  // sizes the scatter's LDS staging block in gr_raster_render
-  return GR_OK;
+  rc = sort_and_count(plan, g, a.P, tot, stream, defer);
+  if (rc != GR_OK || defer != nullptr) return rc;
+  return redo_and_report(plan, a, g, tot, stream, h_num_rendered);
 }
 
 extern "C" int gr_raster_render(int64_t P, const gr_raster_view* h_views, int num_views,
@@ -1607,61 +1604,91 @@ extern "C" int gr_raster_preprocess(int64_t P, int M, const float* means3D, cons
                                     const float* cov3D_precomp, const gr_raster_view* h_views,
                                     int num_views, int32_t* radii, void* geom, size_t geom_bytes,
                                     int64_t* h_num_rendered, void* stream_) {
-  return preprocess_impl(P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, h_views, num_views,
-                         radii, geom, geom_bytes, h_num_rendered, static_cast<hipStream_t>(stream_), nullptr);
+  const SceneArgs a{P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii};
+  return preprocess_impl(a, h_views, num_views, geom, geom_bytes, h_num_rendered, static_cast<hipStream_t>(stream_), nullptr,
+                         false);
 }
 
-// waits for the counts of a deferred preprocess_impl (mailbox stamps or the event): counts -> h_num_rendered;
-// *far_depth = the depth-overflow flag
-// (also set when a bucket of the four-launch depth sort overflowed -- either way the frame has to be redone on the plain
-// path; *bucket_overflow tells the two apart)
-static int preprocess_collect(int64_t P, int num_views, int64_t* h_num_rendered, bool* far_depth, Deferred& d, hipStream_t stream,
-                              bool* bucket_overflow = nullptr) {
-  const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
-  if (d.by_mail) {
-    const volatile int32_t* m = d.mail;
+// has the counting kernel stamped every view's words with this frame's stamp?
+static bool mail_stamped(const volatile int32_t* words, int V, int seq) {
+  bool ready = true;
+  for (int v = 0; v < V; ++v) ready = ready && __atomic_load_n(&words[mail_stamp_word(V, v)], __ATOMIC_ACQUIRE) == seq;
+  return ready;
+}
+
+// waits for the counts of a deferred preprocess_impl (mailbox stamps or the event) and decodes them
+static int preprocess_collect(const Deferred& d, hipStream_t stream, Counts* counts) {
+  const int V = d.plan.V;
+  const volatile int32_t* words = d.mail;
+  if (d.plan.transport == Transport::Mail) {
     // the GPU is still drawing while the host spins here; no time limit of its own (a long or shared device is not an
     // error), but a stream that has drained or failed without the stamps is
     bool ready = false;
     for (unsigned long spin = 1; !ready; ++spin) {
-      ready = true;
-      for (int v = 0; v < num_views; ++v) ready = ready && __atomic_load_n(&m[2 * num_views + 1 + v], __ATOMIC_ACQUIRE) == d.seq;
+      ready = mail_stamped(words, V, d.seq);
       if (!ready && (spin & 0xffff) == 0 && hipStreamQuery(stream) != hipErrorNotReady) {
-        ready = true;
-        for (int v = 0; v < num_views; ++v) ready = ready && __atomic_load_n(&m[2 * num_views + 1 + v], __ATOMIC_ACQUIRE) == d.seq;
+        ready = mail_stamped(words, V, d.seq);
         GR_HIP(hipStreamSynchronize(stream));
         GR_REQUIRE(ready, "rasterizer: the counting kernel did not report its totals");
       }
     }
-    int32_t cm = m[num_views];
-    for (int v = 1; v < num_views; ++v) {
-      const int32_t mv = m[num_views + v];
-      cm = std::max(cm, mv);
-    }
-    for (int v = 0; v < num_views; ++v) h_num_rendered[v] = m[v];
-    h_num_rendered[num_views] = cm;
-    *far_depth = m[2 * num_views] == d.far_seq || m[2 * num_views] == -d.far_seq;
-    if (bucket_overflow) *bucket_overflow = m[2 * num_views] == -d.far_seq;
-    return GR_OK;
+  } else {
+    GR_HIP(hipEventSynchronize(d.ev));
+    words = static_cast<const int32_t*>(pinned_scratch(1, sizeof(int32_t) * (2 * V + 2)));
+    GR_REQUIRE(words != nullptr, "pinned read-back buffer missing");
   }
-  GR_HIP(hipEventSynchronize(d.ev));
-  const int32_t* tot = static_cast<const int32_t*>(pinned_scratch(1, sizeof(int32_t) * (2 * num_views + 2)));
-  GR_REQUIRE(tot != nullptr, "pinned read-back buffer missing");
-  const bool short_rows = nchunk <= SCAN_SINGLE_ROW;
-  int32_t cm = short_rows ? tot[num_views] : tot[2 * num_views + 1];
-  if (short_rows)
-    for (int v = 1; v < num_views; ++v) cm = std::max(cm, tot[num_views + v]);
-  for (int v = 0; v < num_views; ++v) h_num_rendered[v] = tot[v];
-  h_num_rendered[num_views] = cm;
-  *far_depth = tot[2 * num_views] != 0;
-  if (bucket_overflow) *bucket_overflow = tot[2 * num_views] < 0;
+  *counts = decode_counts(words, V, d.plan.short_rows, d.plan.transport, d.far_seq);
   return GR_OK;
 }
 
+using ScatterFn = decltype(&tile_scatter_kernel<true, BIN_T, SEG_READ>);
+static ScatterFn scatter_fn(bool lane_ordered, bool wide, int seg_mode) {
+  // [lane ordered / ballot ranking][SEG_SELF_RAW, SEG_SELF_SCAN, SEG_READ][WIDE_T, BIN_T threads]
+  static const ScatterFn table[2][3][2] = {
+      {{tile_scatter_kernel<true, WIDE_T, SEG_SELF_RAW>, tile_scatter_kernel<true, BIN_T, SEG_SELF_RAW>},
+       {tile_scatter_kernel<true, WIDE_T, SEG_SELF_SCAN>, tile_scatter_kernel<true, BIN_T, SEG_SELF_SCAN>},
+       {tile_scatter_kernel<true, WIDE_T, SEG_READ>, tile_scatter_kernel<true, BIN_T, SEG_READ>}},
+      {{tile_scatter_kernel<false, WIDE_T, SEG_SELF_RAW>, tile_scatter_kernel<false, BIN_T, SEG_SELF_RAW>},
+       {tile_scatter_kernel<false, WIDE_T, SEG_SELF_SCAN>, tile_scatter_kernel<false, BIN_T, SEG_SELF_SCAN>},
+       {tile_scatter_kernel<false, WIDE_T, SEG_READ>, tile_scatter_kernel<false, BIN_T, SEG_READ>}}};
+  return table[lane_ordered ? 0 : 1][seg_mode == SEG_SELF_RAW ? 0 : seg_mode == SEG_SELF_SCAN ? 1 : 2][wide ? 0 : 1];
+}
+
+// the tile scatter of a frame; timed: as the "raster_bin" share of the frame (the launch after a demotion is not)
+static int launch_scatter(bool lane_ordered, bool timed, const FramePlan& plan, const ScatterPlan& sp, const Geom& g, const Bin& b,
+                          int64_t P, unsigned int list_cap, const SelfSeg& self, hipStream_t stream) {
+  const ScatterFn kern = scatter_fn(lane_ordered, sp.threads == WIDE_T, plan.seg_mode);
+  int tile_bits = 0;
+  while ((1 << tile_bits) < plan.tiles) ++tile_bits;
+  if (sp.lds > 64 * 1024)
+    GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               160 * 1024 - 512));  // (the SELF variants hold a few static words as well)
+  std::optional<KernelTimer> timer;
+  if (timed) timer.emplace("raster_bin", stream);
+  hipLaunchKernelGGL(kern, dim3((unsigned)bin_grid(plan.V, plan.nchunk)), dim3(sp.threads), (size_t)sp.lds, stream, (int)P, plan.V,
+                     plan.gx, plan.gy, plan.nchunk, tile_bits, sp.stage_cap, g.nvis, g.rects, g.order_b, g.rec, g.seg_off,
+                     b.point_list, list_cap, sp.elist_cap, self);
+  GR_LAUNCH_CHECK();
+  return GR_OK;
+}
+
+using BlendAuxFn = decltype(&blend_kernel<false, false, true>);
+static BlendAuxFn blend_aux_fn(bool fast, bool keep) {
+  static const BlendAuxFn table[2][2] = {{blend_kernel<true, true, true>, blend_kernel<false, true, true>},
+                                         {blend_kernel<true, false, true>, blend_kernel<false, false, true>}};
+  return table[keep ? 0 : 1][fast ? 0 : 1];
+}
+using BlendFn = decltype(&blend_kernel<false, false>);
+static BlendFn blend_fn(bool fast, bool keep) {
+  static const BlendFn table[2][2] = {{blend_kernel<true, true>, blend_kernel<false, true>},
+                                      {blend_kernel<true, false>, blend_kernel<false, false>}};
+  return table[keep ? 0 : 1][fast ? 0 : 1];
+}
+
 // spec_entries < 0: the instance counts in h_num_rendered are this call's (the normal render).
-// spec_entries >= 0: speculative launch for gr_raster_forward -- the counts are not known on the host yet; `bin` holds
-// spec_entries list entries, h_num_rendered[num_views] is only a hint for the staging block, and the kernels themselves
-// refuse to run past the list (tile_scatter_kernel / blend_kernel list_cap).
+// spec_entries >= 0: speculative launch for gr_raster_forward (defer: that frame) -- the counts are not known on the host
+// yet; `bin` holds spec_entries list entries, h_num_rendered[num_views] is only a hint for the staging block, and the kernels
+// themselves refuse to run past the list (tile_scatter_kernel / blend_kernel list_cap).
 static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, const int64_t* h_num_rendered,
                        const void* geom, size_t geom_bytes, void* bin, size_t bin_bytes, float* out_color, int flags,
                        int64_t spec_entries, hipStream_t stream, const Deferred* defer = nullptr, bool keep = false,
@@ -1671,7 +1698,9 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
   GR_REQUIRE(out_color != nullptr && h_num_rendered != nullptr, "null argument");
   const bool spec = spec_entries >= 0;
   const int W = h_views[0].image_width, H = h_views[0].image_height;
-  const int gx = (W + TILE - 1) / TILE, gy = (H + TILE - 1) / TILE;
+  // (a plain render follows a plain preprocess: the plan of that frame, made again from the same sizes)
+  const FramePlan plan = spec && defer != nullptr ? defer->plan : FramePlan::make(P, num_views, W, H, false, false, false, false);
+  const int gx = plan.gx, gy = plan.gy, tiles = plan.tiles, nchunk = plan.nchunk;
   const int64_t vtiles = (int64_t)gx * gy * num_views;
   GR_REQUIRE(vtiles < (1ll << 31), "too many tiles");
   int64_t R = 0;
@@ -1679,7 +1708,6 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
   else
     for (int v = 0; v < num_views; ++v) R += h_num_rendered[v];
   GR_REQUIRE(R < (1ll << 31) - 1, "too many rendered instances (%lld)", (long long)R);
-  const int tiles = gx * gy;
   Geom g = carve_geom(const_cast<void*>(geom), P, num_views, tiles);
   GR_REQUIRE(P == 0 || (geom && geom_bytes >= g.bytes), "geometry buffer missing or too small");
   Bin b = carve_bin(bin, R, vtiles);
@@ -1687,59 +1715,16 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
     set_error("raster binning buffer too small: need %zu bytes, got %zu", b.bytes, bin_bytes);
     return GR_ERR_WORKSPACE;
   }
-  const int32_t* point_list = b.point_list;
-  const int nchunk = (int)((P + BIN_CHUNK - 1) / BIN_CHUNK);
   const unsigned int list_cap = spec ? (unsigned int)R : 0xffffffffu;
   if (R > 0 || (spec && P > 0)) {
-    // LDS: per-wave 16-bit tile cursors + a staging block that holds a whole chunk's instances (chunks that do not fit write
-    // straight to global memory).  Many views: sized for SCATTER_WGS resident workgroups per CU (the chunks above that take
-    // the direct path), not for the largest chunk -- the scatter is latency-bound and wants the waves
-    // few views: 1024 threads per workgroup (see the kernel) -- as long as their sixteen cursor rows leave room for the staging block
-    const bool wide = num_views <= 4 && (size_t)(WIDE_T / WAVE) * tiles * sizeof(unsigned int) <= 100 * 1024;
-    const int scatter_threads = wide ? WIDE_T : BIN_T;
-    // (the 256-thread scatter counts in a difference grid that IS the wave's cursor row: no LDS beyond the cursors)
-    const size_t cur_bytes = (size_t)(scatter_threads / WAVE) * ((tiles + 1) & ~1) * sizeof(unsigned short);
-    int64_t lds_budget = wide ? 156 * 1024 : 160 * 1024 / SCATTER_WGS - 512;
-    if (lds_budget < (int64_t)cur_bytes + 8 * 1024) lds_budget = 78 * 1024;  // (huge images: two workgroups, as before)
-    const int64_t cap_max = (lds_budget - (int64_t)cur_bytes) / 2;
-    int64_t want = std::max<int64_t>(h_num_rendered[num_views], 0);
-    if (spec) want = want > 0 ? want + 64 : cap_max;  // the hint is last frame's figure; a chunk that outgrows it writes straight
-                                                      // to memory (a 25 % margin here cost a resident workgroup per CU: + 16 % scatter time)
-    int stage_cap = (int)std::min<int64_t>(std::max<int64_t>(cap_max, 0), (want + 63) / 64 * 64);
-    // + per wave the instance list of a step with rectangles of 5 .. 8 tiles a side (see the kernel), when it still fits
-    constexpr int ELIST = 1024;
-    const size_t base_lds = cur_bytes + ((size_t)stage_cap * sizeof(unsigned short) + 3) / 4 * 4;
-    // (only for images whose rectangles are that large: at 640 x 480 the 16 KB would cost a resident workgroup per CU)
-    const int elist_cap = tiles >= 4096 && base_lds + (size_t)(scatter_threads / WAVE) * ELIST * 4 <= 156 * 1024 ? ELIST : 0;
-    const size_t lds = base_lds + (size_t)(scatter_threads / WAVE) * elist_cap * 4;
+    const ScatterPlan sp = ScatterPlan::make(tiles, num_views, h_num_rendered[num_views], spec);
     bool ordered = false;
     rc = lds_atomics_lane_ordered(stream, &ordered);
     if (rc != GR_OK) return rc;
-    const bool self_seg = spec && defer != nullptr && defer->self_seg;
-    const int seg_mode = self_seg ? SEG_SELF_RAW : bin_scans_self(nchunk, num_views) ? SEG_SELF_SCAN : SEG_READ;
-    const SelfSeg self{g.chunk_total, g.totals, self_seg ? const_cast<int32_t*>(defer->mail) : nullptr, self_seg ? defer->seq : 0};
-    auto pick = [&](bool lane_ordered) {
-#define GR_SCATTER(LO, S) (wide ? tile_scatter_kernel<LO, WIDE_T, S> : tile_scatter_kernel<LO, BIN_T, S>)
-      if (lane_ordered)
-        return seg_mode == SEG_SELF_RAW ? GR_SCATTER(true, SEG_SELF_RAW)
-               : seg_mode == SEG_SELF_SCAN ? GR_SCATTER(true, SEG_SELF_SCAN) : GR_SCATTER(true, SEG_READ);
-      return seg_mode == SEG_SELF_RAW ? GR_SCATTER(false, SEG_SELF_RAW)
-             : seg_mode == SEG_SELF_SCAN ? GR_SCATTER(false, SEG_SELF_SCAN) : GR_SCATTER(false, SEG_READ);
-#undef GR_SCATTER
-    };
-    auto kern = pick(ordered);
-    int tile_bits = 0;
-    while ((1 << tile_bits) < tiles) ++tile_bits;
-    if (lds > 64 * 1024)
-      GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 160 * 1024 - 512));  // (the SELF variants hold a few static words as well)
-    {
-      KernelTimer timer("raster_bin", stream);
-      hipLaunchKernelGGL(kern, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(scatter_threads), lds, stream, (int)P, num_views, gx, gy,
-                         nchunk, tile_bits, stage_cap, g.nvis, g.rects, g.order_b, g.rec, g.seg_off, b.point_list, list_cap, elist_cap,
-                         self);
-      GR_LAUNCH_CHECK();
-    }
+    const bool self_raw = plan.seg_mode == SEG_SELF_RAW;
+    const SelfSeg self{g.chunk_total, g.totals, self_raw ? const_cast<int32_t*>(defer->mail) : nullptr, self_raw ? defer->seq : 0};
+    rc = launch_scatter(ordered, true, plan, sp, g, b, P, list_cap, self, stream);
+    if (rc != GR_OK) return rc;
     if (!spec && verify_this_frame()) {  // first frames: every (chunk, tile) segment in depth order?
       int h_bad = 0;
       rc = device_check(stream, [&](int* d_bad) {
@@ -1750,14 +1735,8 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
       if (rc != GR_OK) return rc;
       if (h_bad != 0 && ordered) {
         lds_order_demote();
-        auto kern_b = pick(false);
-        if (lds > 64 * 1024)
-          GR_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern_b), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     160 * 1024 - 512));
-        hipLaunchKernelGGL(kern_b, dim3((unsigned)bin_grid(num_views, nchunk)), dim3(scatter_threads), lds, stream, (int)P,
-                           num_views, gx, gy, nchunk, tile_bits, stage_cap, g.nvis, g.rects, g.order_b, g.rec, g.seg_off,
-                           b.point_list, list_cap, elist_cap, self);
-        GR_LAUNCH_CHECK();
+        rc = launch_scatter(false, false, plan, sp, g, b, P, list_cap, self, stream);
+        if (rc != GR_OK) return rc;
       } else {
         GR_REQUIRE(h_bad == 0, "tile binning produced an unsorted list (internal error)");
       }
@@ -1771,21 +1750,12 @@ static int render_impl(int64_t P, const gr_raster_view* h_views, int num_views, 
   // queue behind it.  14 KB of unused dynamic LDS cap it at 4 workgroups per CU: the blend takes longer, out of sight behind
   // the other frame, and the front chain gets its slots (5 290 -> 5 450 views/s).
   const size_t blend_pad = (spec && (flags & GR_RASTER_SHARE)) ? 14000 : 0;
-#define GR_BLEND(FE, KEEP)                                                                                            \
-  hipLaunchKernelGGL((blend_kernel<FE, KEEP>), dim3(gx, gy, num_views), dim3(BLOCK), blend_pad, stream, (int)P, W, H,      \
-                     blend_chunks, g.views, g.seg_off, point_list, g.rec, out_color, list_cap, BlendAux<false>{})
-#define GR_BLEND_AUX(FE, KEEP)                                                                                        \
-  hipLaunchKernelGGL((blend_kernel<FE, KEEP, true>), dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H,        \
-                     blend_chunks, g.views, g.seg_off, point_list, g.rec, out_color, list_cap,                           \
-                     BlendAux<true>{out_depth, out_alpha, aux_state})
-  if (out_depth != nullptr) {  // gr_raster_render_aux: depth and alpha beside the colour
-    if (keep) { if (fast) GR_BLEND_AUX(true, true); else GR_BLEND_AUX(false, true); }
-    else if (fast) GR_BLEND_AUX(true, false); else GR_BLEND_AUX(false, false);
-  }
-  else if (keep) { if (fast) GR_BLEND(true, true); else GR_BLEND(false, true); }
-  else if (fast) GR_BLEND(true, false); else GR_BLEND(false, false);
-#undef GR_BLEND
-#undef GR_BLEND_AUX
+  if (out_depth != nullptr)  // gr_raster_render_aux: depth and alpha beside the colour
+    hipLaunchKernelGGL(blend_aux_fn(fast, keep), dim3(gx, gy, num_views), dim3(BLOCK), 0, stream, (int)P, W, H, blend_chunks,
+                       g.views, g.seg_off, b.point_list, g.rec, out_color, list_cap, BlendAux<true>{out_depth, out_alpha, aux_state});
+  else
+    hipLaunchKernelGGL(blend_fn(fast, keep), dim3(gx, gy, num_views), dim3(BLOCK), blend_pad, stream, (int)P, W, H, blend_chunks,
+                       g.views, g.seg_off, b.point_list, g.rec, out_color, list_cap, BlendAux<false>{});
   GR_LAUNCH_CHECK();
   frame_done();
   return GR_OK;
@@ -1818,13 +1788,11 @@ namespace gr {
 namespace {
 struct Pending {  // a gr_raster_forward(GR_RASTER_SPLIT) of this thread whose counts have not been collected yet
   bool open;
-  int64_t P;
-  int num_views;
   int64_t entries;
   Deferred d;
   hipStream_t stream;
 };
-thread_local Pending g_pending{false, 0, 0, 0, Deferred{nullptr, nullptr, 0, 0, false, false, false}, nullptr};
+thread_local Pending g_pending{false, 0, Deferred{}, nullptr};
 }  // namespace
 }  // namespace gr
 
@@ -1834,20 +1802,28 @@ extern "C" int gr_raster_debug_bucket_cooldown(int set) {
   return left;
 }
 
+// The second half of a deferred frame: its counts -> h_num_rendered, and what the caller does next.  GR_RETRY_FULL: a depth
+// past the compact keys or an overflowed bucket -- the order is not valid, the frame takes the plain path; GR_RETRY_BIN: the
+// list of `entries` was too short.
+static int collect_deferred(const Deferred& d, int64_t entries, hipStream_t stream, int64_t* h_num_rendered) {
+  Counts c;
+  int rc = preprocess_collect(d, stream, &c);
+  if (rc != GR_OK) return rc;
+  if (c.bucket_overflow) bucket_sort_overflowed();
+  int64_t R = 0;
+  for (int v = 0; v < d.plan.V; ++v) R += h_num_rendered[v] = c.totals[v];
+  h_num_rendered[d.plan.V] = c.chunk_max;
+  if (c.far_depth) return GR_RETRY_FULL;
+  return R <= entries ? GR_OK : GR_RETRY_BIN;
+}
+
 extern "C" int gr_raster_forward_finish(int64_t* h_num_rendered) {
   using namespace gr;
   GR_REQUIRE(g_pending.open, "gr_raster_forward_finish: no split gr_raster_forward is open on this thread");
   GR_REQUIRE(h_num_rendered != nullptr, "h_num_rendered is null");
-  Pending p = g_pending;
+  const Pending p = g_pending;
   g_pending.open = false;
-  bool far_depth = false, bucket_overflow = false;
-  int rc = preprocess_collect(p.P, p.num_views, h_num_rendered, &far_depth, p.d, p.stream, &bucket_overflow);
-  if (rc != GR_OK) return rc;
-  if (bucket_overflow) bucket_sort_overflowed();
-  int64_t R = 0;
-  for (int v = 0; v < p.num_views; ++v) R += h_num_rendered[v];
-  if (far_depth) return GR_RETRY_FULL;
-  return R <= p.entries ? GR_OK : GR_RETRY_BIN;
+  return collect_deferred(p.d, p.entries, p.stream, h_num_rendered);
 }
 
 extern "C" int gr_raster_forward(int64_t P, int M, const float* means3D, const float* shs, const float* colors_precomp,
@@ -1886,25 +1862,21 @@ extern "C" int gr_raster_forward(int64_t P, int M, const float* means3D, const f
       frame_seq.store(1);
       seq = 1;
     }
-    Deferred d{ev, mail, seq, 1, false, bucket_sort_allowed(depth_sort_msd_possible(P, num_views, KEY_DEPTH_BITS)), false};
-    int rc = preprocess_impl(P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, h_views,
-                             num_views, radii, geom, geom_bytes, h_num_rendered, stream, &d);
+    Deferred d{ev, mail, seq, 1, FramePlan{}};
+    const SceneArgs a{P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, radii};
+    int rc = preprocess_impl(a, h_views, num_views, geom, geom_bytes, h_num_rendered, stream, &d,
+                             bucket_sort_allowed(depth_sort_msd_possible(P, num_views, KEY_DEPTH_BITS)));
     if (rc != GR_OK) return rc;
     h_num_rendered[num_views] = stage_hint;
     rc = render_impl(P, h_views, num_views, h_num_rendered, geom, geom_bytes, bin, bin_bytes, out_color, flags, entries, stream,
                      &d);
     if (rc != GR_OK) return rc;
     if (flags & GR_RASTER_SPLIT) {  // the caller comes back with gr_raster_forward_finish (same thread)
-      g_pending = Pending{true, P, num_views, entries, d, stream};
+      g_pending = Pending{true, entries, d, stream};
       return GR_PENDING;
     }
-    bool far_depth = false, bucket_overflow = false;
-    rc = preprocess_collect(P, num_views, h_num_rendered, &far_depth, d, stream, &bucket_overflow);
-    if (rc != GR_OK) return rc;
-    if (bucket_overflow) bucket_sort_overflowed();
-    int64_t R = 0;
-    for (int v = 0; v < num_views; ++v) R += h_num_rendered[v];
-    if (!far_depth) return R <= entries ? GR_OK : GR_RETRY_BIN;
+    rc = collect_deferred(d, entries, stream, h_num_rendered);
+    if (rc != GR_RETRY_FULL) return rc;
     // a depth >= 8192: the ordering has to be redone on full-width keys -- take the plain path for this frame
   }
   int rc = gr_raster_preprocess(P, M, means3D, shs, colors_precomp, opacities, scales, rotations, cov3D_precomp, h_views,

@@ -4,9 +4,10 @@ White box: after gr_raster_preprocess + gr_raster_render_ex on caller-owned buff
 of seg_off (geometry buffer) equal what numpy builds from the same frame's depth order, rectangles and visible counts
 (gr_raster_debug_geom_layout): chunk-major, tiles in order inside a chunk, depth order inside every (chunk, tile) segment.
 Covers the few-view path (count + scan launches), the many-view path (chunk totals only, the scatter scans its own segments),
-the deferred frames of gr_raster_forward (the scatter that scans behind the bucket depth sort), empty views, partial chunks,
-rectangles up to and past 8 tiles a side, marker rectangles, chunks past the staging block and chunks of more than 65 535
-instances -- each with the lane-ordered LDS atomics and with ballot ranking."""
+the deferred frames of gr_raster_forward (the scatter that scans behind the bucket depth sort; with GR_NO_MAILBOX=1 the counts
+that come back behind an event), chunk rows too long for one scan launch (more than 2 048 x 2 048 Gaussians), empty views,
+partial chunks, rectangles up to and past 8 tiles a side, marker rectangles, chunks past the staging block and chunks of more
+than 65 535 instances -- each with the lane-ordered LDS atomics and with ballot ranking."""
 import ctypes
 import math
 import os
@@ -95,11 +96,13 @@ def _chunk_peak(segs):
     return int((segs[:, :, -1] - segs[:, :, 0]).max()) if segs.size else 0
 
 
-def _check_frame(L, geom, binb, P, V, W, H, nr):
+def _check_frame(L, geom, binb, P, V, W, H, nr, min_visible=None):
     off = (ctypes.c_int64 * 4)()
     assert L.gr_raster_debug_geom_layout(P, V, W, H, off) == 4
     torch.cuda.synchronize()
     gh = geom.cpu().numpy()
+    if min_visible is not None:  # every view's depth order is longer than this
+        assert int(gh[off[3]: off[3] + 4 * V].view(np.int32).min()) > min_visible
     want_pl, want_seg, R, markers = _expected(gh, off, P, V, W, H)
     assert [int(nr[v]) for v in range(V)] == [int(want_seg[v, -1, -1] - want_seg[v, 0, 0]) for v in range(V)]
     gx, gy = (W + TILE - 1) // TILE, (H + TILE - 1) // TILE
@@ -113,11 +116,11 @@ def _check_frame(L, geom, binb, P, V, W, H, nr):
     return R, markers, _chunk_peak(want_seg)
 
 
-def _run_plain(P, W, H, V, seed, grow, empty):
+def _run_plain(P, W, H, V, seed, grow, empty, scene=None, min_visible=None):
     from gaussreg_amd import _lib
     from gaussreg_amd.rasterizer import ViewBatch
     L = _lib.lib()
-    t = _scene(P, seed, grow)
+    t = scene if scene is not None else _scene(P, seed, grow)
     vb = ViewBatch(_cams(V, W, H, seed, empty))
     st = _lib.stream_ptr(torch.device("cuda"))
     gbytes = L.gr_raster_geom_bytes(P, V, W, H)
@@ -133,30 +136,32 @@ def _run_plain(P, W, H, V, seed, grow, empty):
     binb = torch.full((bbytes,), 0xAB, dtype=torch.uint8, device="cuda")
     _lib.check(L.gr_raster_render_ex(P, vb.array, V, nr, _lib.ptr(geom), gbytes, _lib.ptr(binb), bbytes, _lib.ptr(color), 0,
                                      st))
-    return _check_frame(L, geom, binb, P, V, W, H, nr)
+    return _check_frame(L, geom, binb, P, V, W, H, nr, min_visible)
 
 
-def _run_deferred(P, W, H, V, seed, grow, frames=5):
+def _run_deferred(P, W, H, V, seed, grow, frames=5, scene=None, last_only=False, bin_bytes=64 << 20, min_visible=None):
     """gr_raster_forward on one buffer set: the first frames of a process are plain (checked), the later ones deferred (a few
-    views per call)."""
+    views per call).  last_only: compare the last frame alone (a deferred one all the same)."""
     from gaussreg_amd import _lib
     from gaussreg_amd.rasterizer import ViewBatch
     L = _lib.lib()
-    t = _scene(P, seed, grow)
+    t = scene if scene is not None else _scene(P, seed, grow)
     vb = ViewBatch(_cams(V, W, H, seed, ()))
     st = _lib.stream_ptr(torch.device("cuda"))
     gbytes = L.gr_raster_geom_bytes(P, V, W, H)
     geom = torch.zeros(gbytes, dtype=torch.uint8, device="cuda")
     radii = torch.empty((V, P), dtype=torch.int32, device="cuda")
     color = torch.empty((V, 3, H, W), dtype=torch.float32, device="cuda")
-    binb = torch.empty(64 << 20, dtype=torch.uint8, device="cuda")
+    binb = torch.empty(bin_bytes, dtype=torch.uint8, device="cuda")
     nr = (ctypes.c_int64 * (V + 1))()
-    for _ in range(frames):
+    for f in range(frames):
         rc = L.gr_raster_forward(P, 16, _lib.ptr(t["means3D"]), _lib.ptr(t["shs"]), None, _lib.ptr(t["opacities"]),
                                  _lib.ptr(t["scales"]), _lib.ptr(t["rotations"]), None, vb.array, V, _lib.ptr(radii),
                                  _lib.ptr(geom), gbytes, _lib.ptr(binb), binb.numel(), _lib.ptr(color), 0, nr, st)
         _lib.check(rc)
-        _check_frame(L, geom, binb, P, V, W, H, nr)
+        if f == frames - 1 or not last_only:
+            out = _check_frame(L, geom, binb, P, V, W, H, nr, min_visible)
+    return out
 
 
 # (P, W, H, V, seed, scale growth, empty views): P not a multiple of 64 or of 2 048 throughout
@@ -210,6 +215,75 @@ def test_deferred_frames_bin_word_for_word(case, ballot):
         L.gr_raster_ballot_ranking(old if old in (0, 1) else 0)
 
 
+# Chunk rows too long for one scan launch: 2 050 chunks (neither a multiple of 64 nor of 2 048) -- chunk_max_kernel, the
+# multi-launch exclusive_scan_i32 and the chunk maximum that travels in a word of its own.
+LONG_P = 2048 * 2048 + 2049
+LONG_W, LONG_H = 64, 64  # 16 tiles: the numpy side stays small
+
+
+def _long_scene(V, seed):
+    """LONG_P Gaussians that are visible in every one of the V views: a small scene is projected once, the Gaussians with a
+    radius in every view are kept and repeated on the device.  Copies have equal depths: ties go by id, the documented rule."""
+    from gaussreg_amd import _lib
+    from gaussreg_amd.rasterizer import ViewBatch
+    L = _lib.lib()
+    P0 = 20011
+    t = _scene(P0, seed, 0.0)
+    vb = ViewBatch(_cams(V, LONG_W, LONG_H, seed, ()))
+    gbytes = L.gr_raster_geom_bytes(P0, V, LONG_W, LONG_H)
+    geom = torch.zeros(gbytes, dtype=torch.uint8, device="cuda")
+    radii = torch.empty((V, P0), dtype=torch.int32, device="cuda")
+    nr = (ctypes.c_int64 * (V + 1))()
+    _lib.check(L.gr_raster_preprocess(P0, 16, _lib.ptr(t["means3D"]), _lib.ptr(t["shs"]), None, _lib.ptr(t["opacities"]),
+                                      _lib.ptr(t["scales"]), _lib.ptr(t["rotations"]), None, vb.array, V, _lib.ptr(radii),
+                                      _lib.ptr(geom), gbytes, nr, _lib.stream_ptr(torch.device("cuda"))))
+    keep = (radii > 0).all(dim=0)
+    n = int(keep.sum())
+    assert n > 1000
+    reps = (LONG_P + n - 1) // n
+    return {k: v[keep].repeat((reps,) + (1,) * (v.dim() - 1))[:LONG_P].contiguous() for k, v in t.items()}
+
+
+@pytest.mark.parametrize("ballot", [0, 1])
+def test_long_chunk_rows_plain_one_view(ballot):
+    from gaussreg_amd import _lib
+    L = _lib.lib()
+    old = L.gr_raster_ballot_ranking(ballot)
+    try:
+        R, _, _ = _run_plain(LONG_P, LONG_W, LONG_H, 1, 8, 0.0, (), scene=_long_scene(1, 8), min_visible=2048 * 2048)
+        assert R > 2048 * 2048
+    finally:
+        L.gr_raster_ballot_ranking(old if old in (0, 1) else 0)
+
+
+@pytest.mark.parametrize("ballot", [0, 1])
+def test_long_chunk_rows_deferred_two_views(ballot):
+    """The fifth frame of the process at the latest is a deferred one: its counts come back behind an event (rows this long
+    are not mailed), the chunk maximum in the last word."""
+    from gaussreg_amd import _lib
+    L = _lib.lib()
+    old = L.gr_raster_ballot_ranking(ballot)
+    try:
+        R, _, _ = _run_deferred(LONG_P, LONG_W, LONG_H, 2, 9, 0.0, scene=_long_scene(2, 9), last_only=True, bin_bytes=256 << 20,
+                                min_visible=2048 * 2048)
+        assert R > 2 * 2048 * 2048
+    finally:
+        L.gr_raster_ballot_ranking(old if old in (0, 1) else 0)
+
+
+@pytest.mark.parametrize("ballot", [0, 1])
+def test_deferred_frames_counts_by_event(ballot):
+    """GR_NO_MAILBOX=1 (read once per process, so in a child process): the counts of a deferred frame come back by a copy on
+    a side stream and an event; with GR_RASTER_BALLOT_RANKING=1 beside it every frame of the process is a deferred one."""
+    env = dict(os.environ, GR_NO_MAILBOX="1")
+    if ballot:
+        env["GR_RASTER_BALLOT_RANKING"] = "1"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "event"], env=env, capture_output=True, text=True,
+                       timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "event path compared" in r.stdout
+
+
 def test_every_frame_verified_on_the_device():
     """GR_RASTER_VERIFY=1 (set before the library loads, so in a child process): the on-device list check runs on every frame."""
     env = dict(os.environ, GR_RASTER_VERIFY="1")
@@ -224,3 +298,9 @@ if __name__ == "__main__" and sys.argv[1:] == ["verify"]:
         _run_plain(*c)
     _run_deferred(30001, 640, 480, 3, 2, 0.02)
     print("verified")
+
+if __name__ == "__main__" and sys.argv[1:] == ["event"]:
+    assert os.environ.get("GR_NO_MAILBOX") == "1"
+    _run_deferred(20011, 640, 480, 1, 1, 0.0)
+    _run_deferred(30001, 640, 480, 3, 2, 0.02)
+    print("event path compared")
