@@ -27,10 +27,17 @@ _CLOUD_NN = ("compute_overlap", "get_correspondences", "compute_modified_chamfer
 # `gaussreg_amd.icp(src, ref, ...)` and `from gaussreg_amd import icp; icp(src, ref, ...)` both run it.
 _ICP = ("icp", "evaluate_registration", "IcpResult")
 
+# nearest neighbours in feature space and the reference's descriptor matching on them (gaussreg_amd.feature_nn)
+_FEATURE_NN = ("feature_nn", "extract_corr_indices_from_feats", "extract_correspondences_from_feats")
+
 
 def __getattr__(name):
-    """The training losses and metrics (gaussreg_amd.loss), the evaluation functions (gaussreg_amd.cloud_nn) and ICP
-    (gaussreg_amd.icp), imported on first use like `differentiable`."""
+    """The training losses and metrics (gaussreg_amd.loss), the evaluation functions (gaussreg_amd.cloud_nn), ICP
+    (gaussreg_amd.icp) and descriptor matching (gaussreg_amd.feature_nn), imported on first use like `differentiable`."""
+    if name in _FEATURE_NN:
+        import importlib
+        module = importlib.import_module(".feature_nn", __name__)
+        return module if name == "feature_nn" else getattr(module, name)
     if name in _ICP:
         import importlib
         module = importlib.import_module(".icp", __name__)

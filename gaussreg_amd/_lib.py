@@ -7,7 +7,8 @@ TRAIN_DEFINES, and those of the matching stage in include/gaussreg_hip_train_mat
 MATCH_TRAIN_DEFINES, and those of the backbone's normalisation layers in include/gaussreg_hip_train_backbone.h into
 BACKBONE_TRAIN_SIGNATURES / BACKBONE_TRAIN_DEFINES, and the cross-cloud nearest-neighbour entry points of
 include/gaussreg_hip_cloud.h into CLOUD_SIGNATURES / CLOUD_DEFINES, and point-to-point ICP of include/gaussreg_hip_icp.h into
-ICP_SIGNATURES / ICP_DEFINES; `lib()` binds the six tables.  Only the three structs
+ICP_SIGNATURES / ICP_DEFINES, and the feature-space nearest neighbours of include/gaussreg_hip_feature_nn.h into
+FEATURE_NN_SIGNATURES / FEATURE_NN_DEFINES; `lib()` binds the seven tables.  Only the three structs
 that cross the boundary are mirrored by hand (they hold arrays).  A declaration the parser does not understand raises.
 
 `call` is the one way a wrapper enters the library: it turns tensors into device pointers after checking that they are
@@ -25,6 +26,7 @@ MATCH_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_tra
 BACKBONE_TRAIN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_train_backbone.h")   # ... of the backbone's norms
 CLOUD_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_cloud.h")   # cross-cloud nearest neighbours
 ICP_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_icp.h")   # point-to-point ICP
+FEATURE_NN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_feature_nn.h")   # feature-space nearest neighbours
 
 _lib = None
 
@@ -116,6 +118,8 @@ with open(CLOUD_HEADER_PATH) as _f:
     CLOUD_SIGNATURES, CLOUD_DEFINES = parse_header(_f.read())
 with open(ICP_HEADER_PATH) as _f:
     ICP_SIGNATURES, ICP_DEFINES = parse_header(_f.read())
+with open(FEATURE_NN_HEADER_PATH) as _f:
+    FEATURE_NN_SIGNATURES, FEATURE_NN_DEFINES = parse_header(_f.read())
 
 GR_PENDING = DEFINES["GR_PENDING"]        # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
 GR_RETRY_FULL = DEFINES["GR_RETRY_FULL"]  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward
@@ -124,6 +128,7 @@ GS_ADAM_MAX_GROUPS = DEFINES["GR_GS_ADAM_MAX_GROUPS"]
 GS_KNN_MAX_K = DEFINES["GR_GS_KNN_MAX_K"]
 CLOUD_KNN_MAX_K = CLOUD_DEFINES["GR_CLOUD_KNN_MAX_K"]
 CLOUD_ICP_MAX_ITERATIONS = ICP_DEFINES["GR_CLOUD_ICP_MAX_ITERATIONS"]
+FEATURE_NN_MAX_C = FEATURE_NN_DEFINES["GR_FEATURE_NN_MAX_C"]
 GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = (DEFINES["GR_GS_DENSIFY_" + r] for r in ("CARRIED", "XYZ", "SCALING"))
 
 
@@ -146,7 +151,8 @@ def lib():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in (list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                    + list(MATCH_TRAIN_SIGNATURES.items()) + list(BACKBONE_TRAIN_SIGNATURES.items())
-                                   + list(CLOUD_SIGNATURES.items()) + list(ICP_SIGNATURES.items())):
+                                   + list(CLOUD_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
+                                   + list(FEATURE_NN_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

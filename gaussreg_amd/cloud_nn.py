@@ -205,8 +205,8 @@ def array_api(fn, clouds):
     def out(v):
         if isinstance(v, torch.Tensor):
             return v.cpu().numpy()
-        if isinstance(v, tuple):
-            return tuple(out(x) for x in v)
+        if isinstance(v, (tuple, list)):
+            return type(v)(out(x) for x in v)
         if isinstance(v, dict):
             return {k: out(x) for k, x in v.items()}
         return np.float64(v) if isinstance(v, float) else v

@@ -30,6 +30,24 @@ def registration_with_ransac_from_correspondences(src_points, ref_points, corres
 
 
 @torch.no_grad()
+def registration_with_ransac_from_feats(src_points, ref_points, src_feats, ref_feats, distance_threshold=0.05, ransac_n=3,
+                                        num_iterations=50000, mutual=False, seed=0):
+    """The reference wrapper of Open3D's registration_ransac_based_on_feature_matching (open3d.py:133-166), rigid: every
+    source point is paired with the reference point whose descriptor is nearest (gaussreg_amd.feature_nn, fp32 features on
+    the GPU; `mutual`: only the pairs that are each other's nearest), then gr_ransac_similarity without scaling runs on
+    the pairs.  Returns a (4,4) float32 tensor; fewer than ransac_n pairs raise.  PARITY UNPINNED: Open3D is not in the
+    reference tree and its sampler is unseeded, and its edge-length checker (CorrespondenceCheckerBasedOnEdgeLength) is not
+    reproduced -- hypotheses are judged by their inlier count alone."""
+    from . import feature_nn
+    src_idx, ref_idx = feature_nn.extract_corr_indices_from_feats(src_feats, ref_feats, mutual=mutual)
+    if src_idx.shape[0] < int(ransac_n):
+        raise ValueError(f"registration_with_ransac_from_feats: {src_idx.shape[0]} pairs, fewer than ransac_n = {ransac_n}")
+    corr = torch.stack([src_idx, ref_idx], dim=1)
+    return registration_with_ransac_from_correspondences(src_points, ref_points, corr, distance_threshold, ransac_n,
+                                                         num_iterations, with_scaling=False, seed=seed)
+
+
+@torch.no_grad()
 def registration_with_ransac_batch(src_points, ref_points, row_offsets, fallback_transforms=None, distance_threshold=0.05,
                                    ransac_n=3, num_iterations=10000, with_scaling=True, refine=True, seed=0,
                                    return_stats=False):

@@ -70,3 +70,31 @@ def cloud_200k(batch=1, seed=0):
     g = torch.Generator().manual_seed(seed)
     pts = (torch.rand(200000 * batch, 3, generator=g) * 10 ** (1 / 3)).float()
     return pts, torch.tensor([200000] * batch, dtype=torch.int64)
+
+
+def descriptor_pair(n=2000, c=32, outlier_frac=0.3, noise=0.02, seed=0):
+    """A registration pair with planted descriptors: ref = n random points of a 4 m cube with unit N(0,1) descriptors; src =
+    a permuted, rigidly moved copy (ref = R src + t) whose descriptors are the ref rows plus `noise`, `outlier_frac` of
+    them replaced by random unit rows.  -> dict of float32 / int64 numpy arrays: ref_points, src_points, ref_feats,
+    src_feats, transform (4, 4, src -> ref), perm (src row i is ref row perm[i]), planted (bool: src row i kept its
+    descriptor)."""
+    rng = np.random.default_rng(seed)
+    ref = rng.random((n, 3)) * 4.0
+    feats = rng.normal(size=(n, c))
+    feats /= np.linalg.norm(feats, axis=1, keepdims=True)
+    ax = rng.normal(size=3)
+    ax /= np.linalg.norm(ax)
+    ang = 0.9
+    K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+    R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * K @ K
+    t = np.array([0.7, -1.2, 0.5])
+    perm = rng.permutation(n)
+    src = (ref[perm] - t) @ R                      # R^T (ref - t)
+    src_feats = feats[perm] + rng.normal(0, noise, (n, c))
+    planted = rng.random(n) >= outlier_frac
+    junk = rng.normal(size=(int((~planted).sum()), c))
+    src_feats[~planted] = junk / np.linalg.norm(junk, axis=1, keepdims=True)
+    T = np.eye(4)
+    T[:3, :3], T[:3, 3] = R, t
+    return {"ref_points": ref.astype(np.float32), "src_points": src.astype(np.float32), "ref_feats": feats.astype(np.float32),
+            "src_feats": src_feats.astype(np.float32), "transform": T, "perm": perm.astype(np.int64), "planted": planted}
