@@ -15,6 +15,8 @@ the GPU through gaussreg_amd:
                                                               # ratio, modified chamfer distance (gaussreg_amd.cloud_nn)
     python examples/register_scenes.py --synthetic --icp      # ... the coarse transform refined by point-to-point ICP on ALL
                                                               # Gaussian centres (gaussreg_amd.icp) before the scenes are fused
+    python examples/register_scenes.py --synthetic --icp --icp_plane   # ... by point-to-plane ICP on PCA normals of the
+                                                              # reference centres (8 neighbours): rigid, keeps the coarse scale
 
 Without --weights the network runs on random weights (the stages run, the estimate is meaningless); the reference's
 checkpoint format (`state_dict["model"]`, demo.py:141-142) loads as is.
@@ -90,7 +92,13 @@ def main():
     ap.add_argument("--icp", action="store_true", help="refine the coarse transform by ICP on all Gaussian centres before fusing")
     ap.add_argument("--icp_dist", type=float, default=0.1, help="largest correspondence distance of --icp, in scene units")
     ap.add_argument("--icp_scale", action="store_true", help="--icp fits a uniform scale as well")
+    ap.add_argument("--icp_plane", action="store_true",
+                    help="--icp refines by point-to-plane ICP on normals of the reference centres (rigid: not with --icp_scale)")
     args = ap.parse_args()
+    if args.icp_plane and args.icp_scale:
+        ap.error("--icp_plane is rigid: it cannot be combined with --icp_scale")
+    if args.icp_plane and not args.icp:
+        ap.error("--icp_plane chooses the estimator of --icp: give --icp as well")
     dev = torch.device("cuda", 0)
     os.makedirs(args.output_path, exist_ok=True)
     T_gt = None
@@ -124,7 +132,7 @@ def main():
                                         pair["ref_adjust_scale"], pair["src_adjust_scale"])
     T_coarse = T
     if args.icp:
-        T = refine_icp(rec_ref, rec_src, T, args.icp_dist, args.icp_scale)
+        T = refine_icp(rec_ref, rec_src, T, args.icp_dist, args.icp_scale, args.icp_plane)
     np.savez(os.path.join(args.output_path, "estimated_transform.npz"), estimated_transform=T)
     fused = gs_io.gaussian_fuse_records(rec_ref, rec_src, T)
     gs_io.write_gs_ply(os.path.join(args.output_path, "fused.ply"), fused.cpu().numpy())
@@ -160,14 +168,18 @@ def evaluate(ref_points, src_points, out, pair, T_gt, T_est, radius):
     print(f"  modified chamfer distance: {chamfer:.6f}")
 
 
-def refine_icp(rec_ref, rec_src, T, max_dist, with_scale):
-    """Point-to-point ICP from the coarse transform on the centres of ALL Gaussians of the two scenes (the network saw a
-    sample of them); -> the refined (4, 4) float64 transform, or the coarse one when the refinement matches fewer points."""
-    from gaussreg_amd import icp
+def refine_icp(rec_ref, rec_src, T, max_dist, with_scale, plane=False):
+    """ICP from the coarse transform on the centres of ALL Gaussians of the two scenes (the network saw a sample of them):
+    point-to-point, or with `plane` point-to-plane on PCA normals of the reference centres (8 neighbours and the centre
+    itself); -> the refined (4, 4) float64 transform, or the coarse one when the refinement matches fewer points."""
+    from gaussreg_amd import estimate_normals, icp, icp_point_to_plane
     ref, src = rec_ref[:, :3].float().contiguous(), rec_src[:, :3].float().contiguous()
-    res = icp(src, ref, T, max_dist=max_dist, with_scale=with_scale, return_history=True)
+    if plane:
+        res = icp_point_to_plane(src, ref, estimate_normals(ref, k=8), T, max_dist=max_dist, return_history=True)
+    else:
+        res = icp(src, ref, T, max_dist=max_dist, with_scale=with_scale, return_history=True)
     start = res.history[0]
-    print(f"icp ({res.status}, {res.iterations} iterations, max_dist {max_dist:g}): fitness {float(start[14]):.4f} -> {res.fitness:.4f}, "
+    print(f"icp ({'point-to-plane, ' if plane else ''}{res.status}, {res.iterations} iterations, max_dist {max_dist:g}): fitness {float(start[14]):.4f} -> {res.fitness:.4f}, "
           f"inlier rmse {float(start[15]):.6f} -> {res.inlier_rmse:.6f}")
     if res.iterations == 0 or res.fitness < float(start[14]):
         print("icp: the coarse transform is kept")

@@ -40,7 +40,8 @@ def build(force=False, verbose=False):
     headers += [os.path.join(HERE, "..", "include", h) for h in ("gaussreg_hip.h", "gaussreg_hip_train.h",
                                                                  "gaussreg_hip_train_matching.h",
                                                                  "gaussreg_hip_train_backbone.h", "gaussreg_hip_cloud.h",
-                                                                 "gaussreg_hip_icp.h", "gaussreg_hip_feature_nn.h")]
+                                                                 "gaussreg_hip_icp.h", "gaussreg_hip_feature_nn.h",
+                                                                 "gaussreg_hip_icp_plane.h")]
     jobs = []
     objs = []
     for src in sources():

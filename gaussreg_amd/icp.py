@@ -14,6 +14,11 @@ coordinates.  The loop stops when fitness and inlier_rmse both change by less th
 max_iterations ("iteration_limit"), or when fewer than three points match or the fit has no spread ("degenerate": the
 transform is the last valid one).  Two calls give the same bits.  These are the semantics of Open3D's registration_icp
 with TransformationEstimationPointToPoint(with_scaling); parity with Open3D is unpinned.  There is no CPU fallback.
+
+    res = icp_point_to_plane(src, ref, estimate_normals(ref), init_transform=T0, max_dist=0.1)
+
+is the same loop with the point-to-plane update (csrc/cloud_icp_plane.hip): rigid only, the estimator for
+scans of walls, floors and table tops, along which point-to-point slides slowly.
 """
 import ctypes
 import sys
@@ -61,10 +66,8 @@ def _transform0(init_transform):
     return np.ascontiguousarray(t[:3])
 
 
-@torch.no_grad()
-def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=False, max_iterations=30,
-        relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False, return_history=False):
-    """Refine `init_transform` (None: identity) so that it maps src_points onto ref_points -> IcpResult."""
+def _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness, relative_rmse):
+    """The checks both estimators share -> (float32(max_dist^2), relative_fitness, relative_rmse) as floats."""
     _check_cloud(src_points, "src_points")
     _check_cloud(ref_points, "ref_points")
     if ref_points.shape[0] < 1:
@@ -81,6 +84,23 @@ def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=Fa
     relative_fitness, relative_rmse = float(relative_fitness), float(relative_rmse)
     if np.isnan(relative_fitness) or np.isnan(relative_rmse):
         raise ValueError("relative_fitness and relative_rmse must not be NaN")
+    return cap, relative_fitness, relative_rmse
+
+
+def _result(transform, stats, h_status, index, dist2, history):
+    status, iterations = STATUS[h_status[0]], int(h_status[1])
+    fitness, rmse = stats[:2].tolist()
+    return IcpResult(transform=transform, fitness=fitness, inlier_rmse=rmse, iterations=iterations,
+                     converged=status == "converged", status=status, index=index, dist2=dist2,
+                     history=history[:iterations + 1].cpu() if history is not None else None)
+
+
+@torch.no_grad()
+def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=False, max_iterations=30,
+        relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False, return_history=False):
+    """Refine `init_transform` (None: identity) so that it maps src_points onto ref_points -> IcpResult."""
+    cap, relative_fitness, relative_rmse = _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness,
+                                                            relative_rmse)
     t0 = _transform0(init_transform)
     src, ref = src_points.detach(), ref_points.detach()
     dev, n, m = src.device, src.shape[0], ref.shape[0]
@@ -93,17 +113,49 @@ def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=Fa
     _finite(lambda: _lib.call(dev, "gr_cloud_icp", src, n, ref, m, t0.ctypes.data_as(ctypes.c_void_p), cap, int(bool(with_scale)),
                               max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history, h_status,
                               ws=_lib.lib().gr_cloud_icp_workspace_bytes(n, m, max_iterations)))
-    status, iterations = STATUS[h_status[0]], int(h_status[1])
-    fitness, rmse = stats[:2].tolist()
-    return IcpResult(transform=transform, fitness=fitness, inlier_rmse=rmse, iterations=iterations,
-                     converged=status == "converged", status=status, index=index, dist2=dist2,
-                     history=history[:iterations + 1].cpu() if return_history else None)
+    return _result(transform, stats, h_status, index, dist2, history)
 
 
 def evaluate_registration(src_points, ref_points, max_dist, transform=None, return_correspondences=False):
     """Fitness and inlier RMSE of `transform` as it stands (Open3D's evaluate_registration): the max_iterations=0 call."""
     return icp(src_points, ref_points, transform, max_dist=max_dist, max_iterations=0,
                return_correspondences=return_correspondences)
+
+
+@torch.no_grad()
+def icp_point_to_plane(src_points, ref_points, ref_normals, init_transform=None, max_dist=0.1, max_iterations=30,
+                       relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False, return_history=False):
+    """Point-to-plane ICP (csrc/cloud_icp_plane.hip, DESIGN.md 3.14, include/gaussreg_hip_icp_plane.h): the loop of `icp`
+    -- the same evaluation, stop rule, statuses and history -- whose update minimises sum ((T p - q) . n)^2 over the
+    matched pairs, linearised at the current transform and solved in float64 on the device; rigid only.  `ref_normals`
+    (M, 3) fp32, one per reference point (`normals.estimate_normals(ref_points)`), finite, used as given; a zero normal
+    (an invalid row of the normals kernel) drops out of the update.  Fewer than six matches or a system without a unique
+    solution (a single plane) is "degenerate".  Open3D's TransformationEstimationPointToPlane; parity unpinned."""
+    cap, relative_fitness, relative_rmse = _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness,
+                                                            relative_rmse)
+    _check_cloud(ref_normals, "ref_normals")
+    if ref_normals.shape[0] != ref_points.shape[0]:
+        raise ValueError(f"ref_normals: {ref_normals.shape[0]} rows for {ref_points.shape[0]} reference points")
+    if ref_normals.device != ref_points.device:
+        raise ValueError(f"ref_points is on {ref_points.device}, ref_normals on {ref_normals.device}")
+    t0 = _transform0(init_transform)
+    src, ref, normals = src_points.detach(), ref_points.detach(), ref_normals.detach()
+    dev, n, m = src.device, src.shape[0], ref.shape[0]
+    transform = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev) if return_correspondences else None
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
+    history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
+    h_status = (ctypes.c_int * 2)(0, 0)
+    try:
+        _finite(lambda: _lib.call(dev, "gr_cloud_icp_plane", src, n, ref, normals, m, t0.ctypes.data_as(ctypes.c_void_p), cap,
+                                  max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history,
+                                  h_status, ws=_lib.lib().gr_cloud_icp_plane_workspace_bytes(n, m, max_iterations)))
+    except RuntimeError as e:
+        if "normals must be finite" in str(e):
+            raise ValueError("normals must be finite") from None
+        raise
+    return _result(transform, stats, h_status, index, dist2, history)
 
 
 class _CallableModule(types.ModuleType):
