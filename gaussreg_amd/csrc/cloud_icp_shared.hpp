@@ -1,12 +1,24 @@
-// What the two ICP loops share (cloud_icp.hip: point-to-point; cloud_icp_plane.hip: point-to-plane, 3.14):
-// the fp32 transform, the kernels that order the source once and match it every round, the scatter of the reported
-// matches and the workspace.  Each loop adds its own sums and fold kernels.  Everything is in the anonymous namespace, so
-// each of the two files compiles its own copy of the kernels.
+// The ICP loop (DESIGN.md 3.11 point-to-point, 3.14 point-to-plane): the fp32 transform, the kernels that order the source
+// once and match it every round, the block sum, the fold kernel with the history row, the stop rule and the epilogue, the
+// scatter of the reported matches, the workspace and the host driver.  cloud_icp.hip and cloud_icp_plane.hip each add an
+// estimator -- its sums, what a matched pair adds to them and its update -- and instantiate the loop with it.  Everything is in the
+// anonymous namespace, so each of the two files compiles its own copy of the kernels.
+//
+// An estimator E provides
+//   NSUM, I_N, I_S     the number of fp64 sums of a partial row and where n and S = sum d sit among them
+//   MIN_PAIRS          fewer matched pairs are GR_CLOUD_ICP_DEGENERATE
+//   Args               what its kernels need beyond the loop's own arguments, passed by value
+//   ARG_NAMES, args_ok the part of the null-pointer check and of its message that Args adds
+//   add                device: one matched pair (the source point, j, d) into a thread's sums
+//   update             thread 0 of the fold: sums, T_t -> Tn, false if there is no fit
+//   after_grid         host: launches of its own behind the grid build (they may raise bits of the finiteness flag)
+//   flag_text          host: the message for a raised flag
 #pragma once
 #include <cmath>
 
 #include "../../include/gaussreg_hip_icp.h"
 #include "cloud_grid.hpp"
+#include "umeyama.hpp"
 
 namespace gr {
 namespace {
@@ -111,6 +123,121 @@ __global__ __launch_bounds__(THREADS) void icp_fallback_kernel(const float4* __r
   }
 }
 
+// v[N] of every thread -> out[N]: the DPP wave sum, then the wave totals in wave order
+template <int N>
+__device__ __forceinline__ void block_sum(double (&v)[N], double* __restrict__ red, double* __restrict__ out) {
+  const int wave = threadIdx.x / WAVE;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const double w = wave_sum_f64_dpp(v[k]);
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[wave * N + k] = w;
+  }
+  __syncthreads();
+  if (threadIdx.x < N) {
+    double a = red[threadIdx.x];
+    for (int w = 1; w < THREADS / WAVE; ++w) a += red[w * N + threadIdx.x];
+    out[threadIdx.x] = a;
+  }
+}
+
+// workgroup b: positions [b SUM_CHUNK, (b + 1) SUM_CHUNK) of the ordered source, thread t takes t, t + 256, .. of the chunk
+// in order and adds each matched pair to its sums by the estimator's `add`, then the DPP wave sum and the four wave totals
+// in wave order -> row b of partial.  The walk is unrolled by the pragma: left to itself the compiler unrolls it when the
+// body is written out here and not when it is a call, which costs point-to-point 8 VGPRs and a wave per SIMD.
+template <class E>
+__global__ __launch_bounds__(THREADS) void icp_sums_kernel(const float4* __restrict__ q_sorted, const float* __restrict__ ref,
+                                const int32_t* __restrict__ match_j, const float* __restrict__ match_d, int32_t nq,
+                                const int32_t* __restrict__ misc, const float* __restrict__ T, typename E::Args args,
+                                double* __restrict__ partial) {
+  constexpr int N = E::NSUM;
+  __shared__ double red[(THREADS / WAVE) * N];
+  if (misc[M_FLAG] | misc[M_DONE]) return;
+  double v[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = 0.0;
+  const int64_t base = (int64_t)blockIdx.x * SUM_CHUNK + threadIdx.x;
+#pragma unroll
+  for (int it = 0; it < SUM_ITEMS; ++it) {
+    const int64_t s = base + (int64_t)it * THREADS;
+    if (s >= nq) break;
+    const int32_t j = match_j[s];
+    if (j < 0) continue;
+    E::add(v, q_sorted[s], j, match_d[s], ref, T, args);
+  }
+  block_sum(v, red, partial + (int64_t)blockIdx.x * N);
+}
+
+// ONE workgroup: thread t adds rows t, t + 256, .. in order, the tree of block_sum; thread 0 records history[t], applies the
+// stop rule, runs the estimator's update and stores T_(t+1), t + 1 -- or done, the status, transform_out and stats_out
+template <class E>
+__global__ __launch_bounds__(THREADS) void icp_fold_kernel(const double* __restrict__ partial, int32_t rows, int32_t nq,
+                                                           int32_t* __restrict__ misc, float* __restrict__ T,
+                                                           double* __restrict__ prev, typename E::Args args,
+                                                           int max_iterations, double relative_fitness, double relative_rmse,
+                                                           double* __restrict__ history, float* __restrict__ transform_out,
+                                                           double* __restrict__ stats_out) {
+  constexpr int N = E::NSUM;
+  __shared__ double red[(THREADS / WAVE) * N];
+  __shared__ double sum[N];
+  if (misc[M_FLAG] | misc[M_DONE]) return;
+  double v[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) v[k] = 0.0;
+  for (int32_t r = threadIdx.x; r < rows; r += THREADS) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] += partial[(int64_t)r * N + k];
+  }
+  block_sum(v, red, sum);
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  const int t = misc[M_ITER];
+  const double n = sum[E::I_N], S = sum[E::I_S];
+  const double fitness = nq > 0 ? n / (double)nq : 0.0, rmse = n > 0.0 ? sqrt(S / n) : 0.0;
+  if (history) {
+    double* h = history + (int64_t)t * HISTORY_ROW;
+    for (int k = 0; k < 12; ++k) h[k] = (double)T[k];
+    h[12] = n;
+    h[13] = S;
+    h[14] = fitness;
+    h[15] = rmse;
+  }
+  int status = 0;
+  if (nq == 0) {
+    status = GR_CLOUD_ICP_DEGENERATE;
+  } else if (t >= 1 && fabs(fitness - prev[0]) < relative_fitness && fabs(rmse - prev[1]) < relative_rmse) {
+    status = GR_CLOUD_ICP_CONVERGED;
+  } else if (t == max_iterations) {
+    status = GR_CLOUD_ICP_ITERATION_LIMIT;
+  } else if (n < E::MIN_PAIRS) {
+    status = GR_CLOUD_ICP_DEGENERATE;
+  } else {
+    float Tn[12];
+    bool ok = E::update(sum, T, args, Tn);
+    for (int k = 0; k < 12; ++k) ok = ok && isfinite(Tn[k]);
+    if (ok) {
+      for (int k = 0; k < 12; ++k) T[k] = Tn[k];
+    } else {
+      status = GR_CLOUD_ICP_DEGENERATE;
+    }
+  }
+  if (status) {
+    for (int k = 0; k < 12; ++k) transform_out[k] = T[k];
+    transform_out[12] = transform_out[13] = transform_out[14] = 0.f;
+    transform_out[15] = 1.f;
+    stats_out[0] = fitness;
+    stats_out[1] = rmse;
+    stats_out[2] = n;
+    stats_out[3] = S;
+    misc[M_STATUS] = status;
+    misc[M_DONE] = 1;
+  } else {
+    prev[0] = fitness;
+    prev[1] = rmse;
+    misc[M_LIST] = 0;  // the list of this round has been consumed
+    misc[M_ITER] = t + 1;
+  }
+}
+
 __global__ __launch_bounds__(THREADS) void icp_scatter_kernel(const float4* __restrict__ q_sorted,
                                                               const int32_t* __restrict__ match_j,
                                                               const float* __restrict__ match_d, int32_t nq,
@@ -173,9 +300,90 @@ IcpWorkspace carve_icp(void* ws, int64_t nq, int64_t ns, int nsum) {
   return w;
 }
 
-bool icp_shape_ok(int64_t nq, int64_t ns, int max_iterations) {
-  return nq >= 0 && nq < (1ll << 31) && ns >= 1 && ns < (1ll << 31) && max_iterations >= 0 &&
-         max_iterations <= GR_CLOUD_ICP_MAX_ITERATIONS;
+template <class E>
+size_t icp_workspace_bytes(int64_t nq, int64_t ns, int max_iterations) {
+  const bool ok = nq >= 0 && nq < (1ll << 31) && ns >= 1 && ns < (1ll << 31) && max_iterations >= 0 &&
+                  max_iterations <= GR_CLOUD_ICP_MAX_ITERATIONS;
+  return ok ? carve_icp(nullptr, nq, ns, E::NSUM).bytes : 0;
+}
+
+// The host side of a call: the checks, the grid over ref and the order of the source, max_iterations + 1 rounds enqueued
+// blindly -- round max_iterations always stops -- the scatter, and the call's one read-back: flag, status, iteration count.
+// `name` opens every message ("cloud icp"); the two timers cover the set-up and the rounds.
+template <class E>
+int icp_run(const char* name, const char* grid_timer, const char* iterate_timer, const float* src, int64_t nq, const float* ref,
+            int64_t ns, const float* h_transform0, float max_dist2, typename E::Args args, int max_iterations,
+            double relative_fitness, double relative_rmse, float* transform_out, double* stats_out, int64_t* index,
+            float* dist2, double* history, int* h_status, void* ws, size_t ws_bytes, hipStream_t stream) {
+  GR_REQUIRE(nq >= 0 && nq < (1ll << 31), "%s: n_src = %lld outside [0, 2^31)", name, (long long)nq);
+  GR_REQUIRE(ns >= 1 && ns < (1ll << 31), "%s: n_ref = %lld outside [1, 2^31)", name, (long long)ns);
+  GR_REQUIRE(max_iterations >= 0 && max_iterations <= GR_CLOUD_ICP_MAX_ITERATIONS, "%s: max_iterations = %d outside [0, %d]",
+             name, max_iterations, GR_CLOUD_ICP_MAX_ITERATIONS);
+  GR_REQUIRE(max_dist2 >= 0.f && std::isfinite(max_dist2), "%s: max_dist2 = %g must be finite and >= 0", name, (double)max_dist2);
+  GR_REQUIRE(!std::isnan(relative_fitness) && !std::isnan(relative_rmse), "%s: a NaN tolerance", name);
+  GR_REQUIRE(ref && E::args_ok(args) && (src || nq == 0) && h_transform0 && transform_out && stats_out && h_status,
+             "%s: null points, %sh_transform0, transform_out, stats_out or h_status", name, E::ARG_NAMES);
+  Transform0 T0;
+  for (int k = 0; k < 12; ++k) {
+    GR_REQUIRE(std::isfinite(h_transform0[k]), "%s: h_transform0[%d] is not finite", name, k);
+    T0.m[k] = h_transform0[k];
+  }
+  const IcpWorkspace w = carve_icp(ws, nq, ns, E::NSUM);
+  if (!ws || ws_bytes < w.bytes) {
+    set_error("%s: workspace of %zu bytes, %zu needed", name, ws_bytes, w.bytes);
+    return GR_ERR_WORKSPACE;
+  }
+  const int D = cloud_grid_dim(ns);
+  const unsigned blocks = (unsigned)((nq + THREADS - 1) / THREADS);
+  if (nq == 0) {
+    GR_HIP(hipMemsetAsync(w.g.misc, 0, MISC * sizeof(int32_t), stream));
+  } else {
+    KernelTimer timer(grid_timer, stream);
+    int rc = cloud_build_support_grid(ref, ns, w.g, w.g.count, w.zero_bytes, stream);
+    if (rc != GR_OK) return rc;
+    E::after_grid(args, ns, w.g.misc, stream);
+    hipLaunchKernelGGL(icp_key_kernel, dim3(blocks), dim3(THREADS), 0, stream, src, nq, T0, D, w.g.B, w.keys_in, w.g.misc);
+    GR_LAUNCH_CHECK();
+    int bits = 1;
+    while ((1ll << bits) < (int64_t)D * D * D) ++bits;
+    rc = sort_pairs_u64_iota(w.sort_temp, w.sort_bytes, w.keys_in, w.keys_out, nq, w.order, nq, 0, bits, stream);
+    if (rc != GR_OK) return rc;
+    hipLaunchKernelGGL(icp_gather_kernel, dim3(blocks), dim3(THREADS), 0, stream, src, w.order, nq, w.q_sorted);
+    GR_LAUNCH_CHECK();
+  }
+  {
+    KernelTimer timer(iterate_timer, stream);
+    hipLaunchKernelGGL(icp_init_kernel, dim3(1), dim3(WAVE), 0, stream, T0, w.T);
+    GR_LAUNCH_CHECK();
+    const unsigned qblocks = (unsigned)((nq + QUERY_THREADS - 1) / QUERY_THREADS);
+    const int64_t waves = (nq + (THREADS / WAVE) - 1) / (THREADS / WAVE);
+    const unsigned fblocks = (unsigned)(waves < FALLBACK_BLOCKS ? waves : FALLBACK_BLOCKS);
+    for (int round = 0; round <= (nq == 0 ? 0 : max_iterations); ++round) {
+      if (nq > 0) {
+        hipLaunchKernelGGL(icp_match_kernel, dim3(qblocks), dim3(QUERY_THREADS), 0, stream, w.g.sorted, w.g.count, w.q_sorted,
+                           w.g.B, w.g.misc, w.T, (int32_t)nq, D, max_dist2, w.match_j, w.match_d, w.list);
+        hipLaunchKernelGGL(icp_fallback_kernel, dim3(fblocks), dim3(THREADS), 0, stream, w.g.sorted, (int32_t)ns, w.q_sorted,
+                           w.list, w.g.misc, w.T, max_dist2, w.match_j, w.match_d);
+        hipLaunchKernelGGL(icp_sums_kernel<E>, dim3(w.rows), dim3(THREADS), 0, stream, w.q_sorted, ref, w.match_j, w.match_d,
+                           (int32_t)nq, w.g.misc, w.T, args, w.partial);
+      }
+      hipLaunchKernelGGL(icp_fold_kernel<E>, dim3(1), dim3(THREADS), 0, stream, w.partial, w.rows, (int32_t)nq, w.g.misc, w.T,
+                         w.prev, args, max_iterations, relative_fitness, relative_rmse, history, transform_out, stats_out);
+      GR_LAUNCH_CHECK();
+    }
+    if (nq > 0 && (index || dist2)) {
+      hipLaunchKernelGGL(icp_scatter_kernel, dim3(blocks), dim3(THREADS), 0, stream, w.q_sorted, w.match_j, w.match_d, (int32_t)nq,
+                         w.g.misc, index, dist2);
+      GR_LAUNCH_CHECK();
+    }
+  }
+  int32_t h_misc[MISC];
+  GR_HIP(hipMemcpyAsync(h_misc, w.g.misc, sizeof h_misc, hipMemcpyDeviceToHost, stream));
+  GR_HIP(hipStreamSynchronize(stream));
+  GR_REQUIRE(h_misc[M_FLAG] == 0, "%s: %s", name, E::flag_text(h_misc[M_FLAG]));
+  h_status[0] = h_misc[M_STATUS];
+  h_status[1] = h_misc[M_ITER];
+  return GR_OK;
 }
 
 }  // namespace

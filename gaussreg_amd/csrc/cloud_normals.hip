@@ -3,15 +3,14 @@
 //
 //   normals_kernel   one thread per query: gathers the listed support points (an entry outside [0, M) is padding), the
 //                    query first when include_self; every point minus the FIRST of the set in fp64 (exact), sum d and
-//                    sum d d^T in list order, C = sum d d^T - (sum d)(sum d)^T / m; cyclic Jacobi of the 3x3 in fp64 with
-//                    compile-time indices only (the pattern of jacobi_maxvec4, umeyama.hpp: a run-time column index would
-//                    put the matrices into scratch); the eigenvector of the smallest eigenvalue by selects, the sign, one
-//                    rounding to fp32.
+//                    sum d d^T in list order, C = sum d d^T - (sum d)(sum d)^T / m; cyclic Jacobi of the 3x3 in fp64
+//                    (jacobi_sym, umeyama.hpp: compile-time indices only); the eigenvector of the smallest eigenvalue
+//                    by selects, the sign, one rounding to fp32.
 // The gather dominates: per query K indices of 8 B and up to K + 1 scattered points of 12 B.
 #include <cmath>
 
 #include "../../include/gaussreg_hip_icp_plane.h"
-#include "common.hpp"
+#include "umeyama.hpp"
 
 namespace gr {
 namespace {
@@ -23,34 +22,6 @@ struct Toward {
   float p[3];
   int given;
 };
-
-// A (symmetric, destroyed) -> eigenvalues on its diagonal, eigenvectors in the columns of V
-__device__ __forceinline__ void jacobi3(double (&A)[3][3], double (&V)[3][3]) {
-  double fro2 = 0.0;
-#pragma unroll
-  for (int p = 0; p < 3; ++p)
-#pragma unroll
-    for (int r = 0; r < 3; ++r) fro2 += A[p][r] * A[p][r];
-  for (int sweep = 0; sweep < NORMALS_SWEEPS; ++sweep) {
-    const double off = (A[0][1] * A[0][1] + A[0][2] * A[0][2]) + A[1][2] * A[1][2];
-    if (off <= 1e-30 * fro2) break;
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-      for (int r = p + 1; r < 3; ++r) {
-        if (fabs(A[p][r]) < 1e-300) continue;
-        const double theta = (A[r][r] - A[p][p]) / (2.0 * A[p][r]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double a = A[k][p], b = A[k][r]; A[k][p] = c * a - s * b; A[k][r] = s * a + c * b; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double a = A[p][k], b = A[r][k]; A[p][k] = c * a - s * b; A[r][k] = s * a + c * b; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { const double a = V[k][p], b = V[k][r]; V[k][p] = c * a - s * b; V[k][r] = s * a + c * b; }
-      }
-  }
-}
 
 __global__ __launch_bounds__(NORMALS_THREADS) void normals_kernel(const float* __restrict__ query, int64_t n,
                                                                   const float* support, int64_t M,
@@ -82,14 +53,14 @@ __global__ __launch_bounds__(NORMALS_THREADS) void normals_kernel(const float* _
   uint8_t ok = 0;
   if (m >= 3) {
     const double mm = (double)m;
-    double A[3][3], V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    double A[3][3], V[3][3];
     A[0][0] = xx - s[0] * s[0] / mm;
     A[0][1] = A[1][0] = xy - s[0] * s[1] / mm;
     A[0][2] = A[2][0] = xz - s[0] * s[2] / mm;
     A[1][1] = yy - s[1] * s[1] / mm;
     A[1][2] = A[2][1] = yz - s[1] * s[2] / mm;
     A[2][2] = zz - s[2] * s[2] / mm;
-    jacobi3(A, V);
+    jacobi_sym<3, NORMALS_SWEEPS>(A, V);
     const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
     // the smallest (the first among equals), the largest (the last among equals), and the one left over
     const int lo = (e0 <= e1 && e0 <= e2) ? 0 : (e1 <= e2 ? 1 : 2);

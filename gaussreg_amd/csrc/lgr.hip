@@ -10,66 +10,14 @@
 //   verify    one workgroup per hypothesis: inliers (residual < acceptance_radius) over ALL correspondences
 //   refine    one workgroup: best hypothesis -> mask -> weighted Kabsch, num_refinement_steps times
 // Rotation: the proper rotation maximising tr(R H) -- Horn's unit-quaternion form (largest eigenvector of a
-// symmetric 4x4 built from H, cyclic Jacobi in fp64); identical to V diag(1,1,det(VU^T)) U^T of
-// procrustes.py:59-64 whenever that is unique.
-#include "common.hpp"
+// symmetric 4x4 built from H, cyclic Jacobi in fp64: rotation_from_covariance, umeyama.hpp); identical to
+// V diag(1,1,det(VU^T)) U^T of procrustes.py:59-64 whenever that is unique.
+#include "umeyama.hpp"
 
 namespace gr {
 namespace {
 
 constexpr int LG_T = 256;
-
-// largest-eigenvalue eigenvector of symmetric 4x4 A (row-major), cyclic Jacobi
-__device__ void horn_rotation(const double* H /*3x3: H[a][b] = sum w src_a ref_b*/, double* R /*3x3*/) {
-  const double Sxx = H[0], Sxy = H[1], Sxz = H[2], Syx = H[3], Syy = H[4], Syz = H[5], Szx = H[6], Szy = H[7], Szz = H[8];
-  double A[4][4] = {{Sxx + Syy + Szz, Syz - Szy, Szx - Sxz, Sxy - Syx},
-                    {Syz - Szy, Sxx - Syy - Szz, Sxy + Syx, Szx + Sxz},
-                    {Szx - Sxz, Sxy + Syx, -Sxx + Syy - Szz, Syz + Szy},
-                    {Sxy - Syx, Szx + Sxz, Syz + Szy, -Sxx - Syy + Szz}};
-  double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-  // stop when the off-diagonal mass is below fp64 resolution of the matrix (1e-15 of its Frobenius norm): waiting for it
-  // to underflow costs four more sweeps of serial fp64 work in the one thread that runs this
-  double fro2 = 0.0;
-  for (int p = 0; p < 4; ++p)
-    for (int q = 0; q < 4; ++q) fro2 += A[p][q] * A[p][q];
-  for (int sweep = 0; sweep < 16; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 4; ++p)
-      for (int q = p + 1; q < 4; ++q) off += A[p][q] * A[p][q];
-    if (off <= 1e-30 * fro2) break;
-    for (int p = 0; p < 3; ++p)
-      for (int q = p + 1; q < 4; ++q) {
-        if (fabs(A[p][q]) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; ++k) {
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq;
-          A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk;
-          A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 4; ++k) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq;
-          V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  int best = 0;
-  for (int k = 1; k < 4; ++k)
-    if (A[k][k] > A[best][best]) best = k;
-  double w = V[0][best], x = V[1][best], y = V[2][best], z = V[3][best];
-  const double nrm = sqrt(w * w + x * x + y * y + z * z);
-  w /= nrm; x /= nrm; y /= nrm; z /= nrm;
-  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z);     R[2] = 2 * (x * z + w * y);
-  R[3] = 2 * (x * y + w * z);     R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
-  R[6] = 2 * (x * z - w * y);     R[7] = 2 * (y * z + w * x);     R[8] = 1 - 2 * (x * x + y * y);
-}
 
 // block-wide sum of NV doubles per thread -> result in sh[0..NV) (valid for all threads after return)
 template <int NV, int T>
@@ -124,7 +72,7 @@ __device__ void block_procrustes(const float* __restrict__ src, const float* __r
   block_sum<9, NT>(h, sh);
   if (threadIdx.x == 0) {
     double R[9];
-    horn_rotation(h, R);
+    rotation_from_covariance(h, R);
     for (int k = 0; k < 9; ++k) T[k] = (float)R[k];
     for (int r = 0; r < 3; ++r) T[9 + r] = (float)(cr[r] - (R[r * 3] * cs[0] + R[r * 3 + 1] * cs[1] + R[r * 3 + 2] * cs[2]));
   }

@@ -87,7 +87,22 @@ def _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_
     return cap, relative_fitness, relative_rmse
 
 
-def _result(transform, stats, h_status, index, dist2, history):
+def _run(entry, src_points, ref_points, extra_clouds, init_transform, extra_scalars, cap, max_iterations, relative_fitness,
+         relative_rmse, return_correspondences, return_history):
+    """Allocate the outputs, call `entry` -- gr_cloud_icp(src, n, ref, *extra_clouds, m, T0, cap, *extra_scalars, ...) --
+    and read the result."""
+    t0 = _transform0(init_transform)
+    src, ref = src_points.detach(), ref_points.detach()
+    dev, n, m = src.device, src.shape[0], ref.shape[0]
+    transform = torch.empty((4, 4), dtype=torch.float32, device=dev)
+    stats = torch.empty(4, dtype=torch.float64, device=dev)
+    index = torch.empty(n, dtype=torch.int64, device=dev) if return_correspondences else None
+    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
+    history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
+    h_status = (ctypes.c_int * 2)(0, 0)
+    _finite(lambda: _lib.call(dev, entry, src, n, ref, *extra_clouds, m, t0.ctypes.data_as(ctypes.c_void_p), cap, *extra_scalars,
+                              max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history, h_status,
+                              ws=getattr(_lib.lib(), entry + "_workspace_bytes")(n, m, max_iterations)))
     status, iterations = STATUS[h_status[0]], int(h_status[1])
     fitness, rmse = stats[:2].tolist()
     return IcpResult(transform=transform, fitness=fitness, inlier_rmse=rmse, iterations=iterations,
@@ -101,19 +116,8 @@ def icp(src_points, ref_points, init_transform=None, max_dist=0.1, with_scale=Fa
     """Refine `init_transform` (None: identity) so that it maps src_points onto ref_points -> IcpResult."""
     cap, relative_fitness, relative_rmse = _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness,
                                                             relative_rmse)
-    t0 = _transform0(init_transform)
-    src, ref = src_points.detach(), ref_points.detach()
-    dev, n, m = src.device, src.shape[0], ref.shape[0]
-    transform = torch.empty((4, 4), dtype=torch.float32, device=dev)
-    stats = torch.empty(4, dtype=torch.float64, device=dev)
-    index = torch.empty(n, dtype=torch.int64, device=dev) if return_correspondences else None
-    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
-    history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
-    h_status = (ctypes.c_int * 2)(0, 0)
-    _finite(lambda: _lib.call(dev, "gr_cloud_icp", src, n, ref, m, t0.ctypes.data_as(ctypes.c_void_p), cap, int(bool(with_scale)),
-                              max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history, h_status,
-                              ws=_lib.lib().gr_cloud_icp_workspace_bytes(n, m, max_iterations)))
-    return _result(transform, stats, h_status, index, dist2, history)
+    return _run("gr_cloud_icp", src_points, ref_points, (), init_transform, (int(bool(with_scale)),), cap, max_iterations,
+                relative_fitness, relative_rmse, return_correspondences, return_history)
 
 
 def evaluate_registration(src_points, ref_points, max_dist, transform=None, return_correspondences=False):
@@ -138,24 +142,13 @@ def icp_point_to_plane(src_points, ref_points, ref_normals, init_transform=None,
         raise ValueError(f"ref_normals: {ref_normals.shape[0]} rows for {ref_points.shape[0]} reference points")
     if ref_normals.device != ref_points.device:
         raise ValueError(f"ref_points is on {ref_points.device}, ref_normals on {ref_normals.device}")
-    t0 = _transform0(init_transform)
-    src, ref, normals = src_points.detach(), ref_points.detach(), ref_normals.detach()
-    dev, n, m = src.device, src.shape[0], ref.shape[0]
-    transform = torch.empty((4, 4), dtype=torch.float32, device=dev)
-    stats = torch.empty(4, dtype=torch.float64, device=dev)
-    index = torch.empty(n, dtype=torch.int64, device=dev) if return_correspondences else None
-    dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
-    history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
-    h_status = (ctypes.c_int * 2)(0, 0)
     try:
-        _finite(lambda: _lib.call(dev, "gr_cloud_icp_plane", src, n, ref, normals, m, t0.ctypes.data_as(ctypes.c_void_p), cap,
-                                  max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history,
-                                  h_status, ws=_lib.lib().gr_cloud_icp_plane_workspace_bytes(n, m, max_iterations)))
+        return _run("gr_cloud_icp_plane", src_points, ref_points, (ref_normals.detach(),), init_transform, (), cap,
+                    max_iterations, relative_fitness, relative_rmse, return_correspondences, return_history)
     except RuntimeError as e:
         if "normals must be finite" in str(e):
             raise ValueError("normals must be finite") from None
         raise
-    return _result(transform, stats, h_status, index, dist2, history)
 
 
 class _CallableModule(types.ModuleType):

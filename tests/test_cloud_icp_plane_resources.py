@@ -16,8 +16,8 @@ KERNELS = (("icp_init_kernel", {"LDS Size": 0, "VGPRs": 2, "Occupancy": 8}),
            ("icp_fallback_kernel", {"LDS Size": 0, "VGPRs": 29, "Occupancy": 8}),
            ("icp_scatter_kernel", {"LDS Size": 0, "VGPRs": 8, "Occupancy": 8}),
            ("icpp_normals_kernel", {"LDS Size": 0, "VGPRs": 2, "Occupancy": 8}),
-           ("icpp_sums_kernel", {"LDS Size": 928, "VGPRs": 102, "Occupancy": 4}),
-           ("icpp_fold_kernel", {"LDS Size": 1800, "VGPRs": 122, "Occupancy": 4}))
+           ("icp_sums_kernel<PointToPlane>", {"LDS Size": 928, "VGPRs": 98, "Occupancy": 4}),
+           ("icp_fold_kernel<PointToPlane>", {"LDS Size": 1736, "VGPRs": 122, "Occupancy": 4}))
 
 
 def _resources():

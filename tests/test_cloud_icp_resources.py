@@ -14,8 +14,8 @@ KERNELS = (("icp_init_kernel", {"LDS Size": 0, "VGPRs": 2, "Occupancy": 8}),
            ("icp_gather_kernel", {"LDS Size": 0, "VGPRs": 6, "Occupancy": 8}),
            ("icp_match_kernel", {"LDS Size": 0, "VGPRs": 43, "Occupancy": 8}),
            ("icp_fallback_kernel", {"LDS Size": 0, "VGPRs": 29, "Occupancy": 8}),
-           ("icp_sums_kernel", {"LDS Size": 576, "VGPRs": 62, "Occupancy": 8}),
-           ("icp_fold_kernel", {"LDS Size": 720, "VGPRs": 120, "Occupancy": 4}),
+           ("icp_sums_kernel<PointToPoint>", {"LDS Size": 576, "VGPRs": 62, "Occupancy": 8}),
+           ("icp_fold_kernel<PointToPoint>", {"LDS Size": 720, "VGPRs": 126, "Occupancy": 4}),
            ("icp_scatter_kernel", {"LDS Size": 0, "VGPRs": 8, "Occupancy": 8}))
 
 
