@@ -17,6 +17,8 @@ the GPU through gaussreg_amd:
                                                               # Gaussian centres (gaussreg_amd.icp) before the scenes are fused
     python examples/register_scenes.py --synthetic --icp --icp_plane   # ... by point-to-plane ICP on PCA normals of the
                                                               # reference centres (8 neighbours): rigid, keeps the coarse scale
+    python examples/register_scenes.py --synthetic --icp --icp_generalized   # ... by generalised ICP whose covariances are
+                                                              # the plane priors of the scenes' OWN Gaussians (thinnest axis)
 
 Without --weights the network runs on random weights (the stages run, the estimate is meaningless); the reference's
 checkpoint format (`state_dict["model"]`, demo.py:141-142) loads as is.
@@ -94,7 +96,16 @@ def main():
     ap.add_argument("--icp_scale", action="store_true", help="--icp fits a uniform scale as well")
     ap.add_argument("--icp_plane", action="store_true",
                     help="--icp refines by point-to-plane ICP on normals of the reference centres (rigid: not with --icp_scale)")
+    ap.add_argument("--icp_generalized", action="store_true",
+                    help="--icp refines by generalised ICP (rigid: not with --icp_scale, not with --icp_plane)")
+    ap.add_argument("--icp_cov", choices=("gaussians", "neighbors"), default="gaussians",
+                    help="covariances of --icp_generalized: the plane prior about each Gaussian's thinnest axis, from the scenes' "
+                         "own scales and rotations, or about PCA normals of 8 neighbours")
     args = ap.parse_args()
+    if args.icp_generalized and (args.icp_scale or args.icp_plane):
+        ap.error("--icp_generalized is rigid and an estimator of its own: it cannot be combined with --icp_scale or --icp_plane")
+    if args.icp_generalized and not args.icp:
+        ap.error("--icp_generalized chooses the estimator of --icp: give --icp as well")
     if args.icp_plane and args.icp_scale:
         ap.error("--icp_plane is rigid: it cannot be combined with --icp_scale")
     if args.icp_plane and not args.icp:
@@ -132,7 +143,8 @@ def main():
                                         pair["ref_adjust_scale"], pair["src_adjust_scale"])
     T_coarse = T
     if args.icp:
-        T = refine_icp(rec_ref, rec_src, T, args.icp_dist, args.icp_scale, args.icp_plane)
+        T = refine_icp(rec_ref, rec_src, T, args.icp_dist, args.icp_scale, args.icp_plane,
+                       args.icp_cov if args.icp_generalized else None)
     np.savez(os.path.join(args.output_path, "estimated_transform.npz"), estimated_transform=T)
     fused = gs_io.gaussian_fuse_records(rec_ref, rec_src, T)
     gs_io.write_gs_ply(os.path.join(args.output_path, "fused.ply"), fused.cpu().numpy())
@@ -168,18 +180,31 @@ def evaluate(ref_points, src_points, out, pair, T_gt, T_est, radius):
     print(f"  modified chamfer distance: {chamfer:.6f}")
 
 
-def refine_icp(rec_ref, rec_src, T, max_dist, with_scale, plane=False):
+def _covariances(rec, points, source):
+    """The (N, 6) covariances of a scene's centres: the plane prior about the thinnest axis of each Gaussian -- its activated
+    scales and its rotation, columns 55:58 and 58:62 of the record -- or about the PCA normal of 8 neighbours."""
+    from gaussreg_amd import covariances_from_gaussians, estimate_covariances
+    if source == "neighbors":
+        return estimate_covariances(points, k=8)
+    return covariances_from_gaussians(torch.exp(rec[:, 55:58].float()).contiguous(), rec[:, 58:62].float().contiguous(), mode="plane")
+
+
+def refine_icp(rec_ref, rec_src, T, max_dist, with_scale, plane=False, generalized=None):
     """ICP from the coarse transform on the centres of ALL Gaussians of the two scenes (the network saw a sample of them):
     point-to-point, or with `plane` point-to-plane on PCA normals of the reference centres (8 neighbours and the centre
-    itself); -> the refined (4, 4) float64 transform, or the coarse one when the refinement matches fewer points."""
-    from gaussreg_amd import estimate_normals, icp, icp_point_to_plane
+    itself), or with `generalized` ("gaussians" / "neighbors": where the covariances come from) generalised ICP; -> the
+    refined (4, 4) float64 transform, or the coarse one when the refinement matches fewer points."""
+    from gaussreg_amd import estimate_normals, icp, icp_generalized, icp_point_to_plane
     ref, src = rec_ref[:, :3].float().contiguous(), rec_src[:, :3].float().contiguous()
-    if plane:
+    if generalized:
+        res = icp_generalized(src, ref, _covariances(rec_src, src, generalized), _covariances(rec_ref, ref, generalized), T,
+                              max_dist=max_dist, return_history=True)
+    elif plane:
         res = icp_point_to_plane(src, ref, estimate_normals(ref, k=8), T, max_dist=max_dist, return_history=True)
     else:
         res = icp(src, ref, T, max_dist=max_dist, with_scale=with_scale, return_history=True)
     start = res.history[0]
-    print(f"icp ({'point-to-plane, ' if plane else ''}{res.status}, {res.iterations} iterations, max_dist {max_dist:g}): fitness {float(start[14]):.4f} -> {res.fitness:.4f}, "
+    print(f"icp ({'generalised, ' if generalized else 'point-to-plane, ' if plane else ''}{res.status}, {res.iterations} iterations, max_dist {max_dist:g}): fitness {float(start[14]):.4f} -> {res.fitness:.4f}, "
           f"inlier rmse {float(start[15]):.6f} -> {res.inlier_rmse:.6f}")
     if res.iterations == 0 or res.fitness < float(start[14]):
         print("icp: the coarse transform is kept")

@@ -25,10 +25,13 @@ _CLOUD_NN = ("compute_overlap", "get_correspondences", "compute_modified_chamfer
 
 # point-to-point ICP (gaussreg_amd.icp).  `gaussreg_amd.icp` is the submodule, which is callable as its function `icp`:
 # `gaussreg_amd.icp(src, ref, ...)` and `from gaussreg_amd import icp; icp(src, ref, ...)` both run it.
-_ICP = ("icp", "evaluate_registration", "IcpResult", "icp_point_to_plane")
+_ICP = ("icp", "evaluate_registration", "IcpResult", "icp_point_to_plane", "icp_generalized")
 
 # PCA normals from a neighbour table (gaussreg_amd.normals), what point-to-plane ICP takes for its reference cloud
 _NORMALS = ("normals_from_neighbors", "estimate_normals")
+
+# the covariances generalised ICP takes: from normals, from a scene's own Gaussians, or estimated (gaussreg_amd.covariances)
+_COVARIANCES = ("covariances_from_normals", "covariances_from_gaussians", "estimate_covariances")
 
 # nearest neighbours in feature space and the reference's descriptor matching on them (gaussreg_amd.feature_nn)
 _FEATURE_NN = ("feature_nn", "extract_corr_indices_from_feats", "extract_correspondences_from_feats")
@@ -36,11 +39,14 @@ _FEATURE_NN = ("feature_nn", "extract_corr_indices_from_feats", "extract_corresp
 
 def __getattr__(name):
     """The training losses and metrics (gaussreg_amd.loss), the evaluation functions (gaussreg_amd.cloud_nn), ICP
-    (gaussreg_amd.icp), normals (gaussreg_amd.normals) and descriptor matching (gaussreg_amd.feature_nn), imported on first use like `differentiable`."""
+    (gaussreg_amd.icp), normals (gaussreg_amd.normals), covariances (gaussreg_amd.covariances) and descriptor matching (gaussreg_amd.feature_nn), imported on first use like `differentiable`."""
     if name in _FEATURE_NN:
         import importlib
         module = importlib.import_module(".feature_nn", __name__)
         return module if name == "feature_nn" else getattr(module, name)
+    if name in _COVARIANCES:
+        import importlib
+        return getattr(importlib.import_module(".covariances", __name__), name)
     if name in _NORMALS:
         import importlib
         return getattr(importlib.import_module(".normals", __name__), name)

@@ -9,7 +9,8 @@ BACKBONE_TRAIN_SIGNATURES / BACKBONE_TRAIN_DEFINES, and the cross-cloud nearest-
 include/gaussreg_hip_cloud.h into CLOUD_SIGNATURES / CLOUD_DEFINES, and point-to-point ICP of include/gaussreg_hip_icp.h into
 ICP_SIGNATURES / ICP_DEFINES, and the feature-space nearest neighbours of include/gaussreg_hip_feature_nn.h into
 FEATURE_NN_SIGNATURES / FEATURE_NN_DEFINES, and the PCA normals and point-to-plane ICP of
-include/gaussreg_hip_icp_plane.h into ICP_PLANE_SIGNATURES / ICP_PLANE_DEFINES; `lib()` binds the eight tables.  Only the three structs
+include/gaussreg_hip_icp_plane.h into ICP_PLANE_SIGNATURES / ICP_PLANE_DEFINES, and generalised ICP with its covariance
+kernels of include/gaussreg_hip_gicp.h into GICP_SIGNATURES / GICP_DEFINES; `lib()` binds the nine tables.  Only the three structs
 that cross the boundary are mirrored by hand (they hold arrays).  A declaration the parser does not understand raises.
 
 `call` is the one way a wrapper enters the library: it turns tensors into device pointers after checking that they are
@@ -29,6 +30,7 @@ CLOUD_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_cloud.h")
 ICP_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_icp.h")   # point-to-point ICP
 FEATURE_NN_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_feature_nn.h")   # feature-space nearest neighbours
 ICP_PLANE_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_icp_plane.h")   # PCA normals, point-to-plane ICP
+GICP_HEADER_PATH = os.path.join(_HERE, "..", "include", "gaussreg_hip_gicp.h")   # generalised ICP, covariances
 
 _lib = None
 
@@ -124,6 +126,8 @@ with open(FEATURE_NN_HEADER_PATH) as _f:
     FEATURE_NN_SIGNATURES, FEATURE_NN_DEFINES = parse_header(_f.read())
 with open(ICP_PLANE_HEADER_PATH) as _f:
     ICP_PLANE_SIGNATURES, ICP_PLANE_DEFINES = parse_header(_f.read())
+with open(GICP_HEADER_PATH) as _f:
+    GICP_SIGNATURES, GICP_DEFINES = parse_header(_f.read())
 
 GR_PENDING = DEFINES["GR_PENDING"]        # gr_raster_forward(GR_RASTER_SPLIT): enqueued, gr_raster_forward_finish collects the counts
 GR_RETRY_FULL = DEFINES["GR_RETRY_FULL"]  # gr_raster_forward_finish: repeat the frame with an unsplit gr_raster_forward
@@ -134,6 +138,7 @@ CLOUD_KNN_MAX_K = CLOUD_DEFINES["GR_CLOUD_KNN_MAX_K"]
 CLOUD_ICP_MAX_ITERATIONS = ICP_DEFINES["GR_CLOUD_ICP_MAX_ITERATIONS"]
 FEATURE_NN_MAX_C = FEATURE_NN_DEFINES["GR_FEATURE_NN_MAX_C"]
 CLOUD_NORMALS_MAX_K = ICP_PLANE_DEFINES["GR_CLOUD_NORMALS_MAX_K"]
+GS_COV_RAW, GS_COV_PLANE = GICP_DEFINES["GR_GS_COV_RAW"], GICP_DEFINES["GR_GS_COV_PLANE"]
 GS_DENSIFY_CARRIED, GS_DENSIFY_XYZ, GS_DENSIFY_SCALING = (DEFINES["GR_GS_DENSIFY_" + r] for r in ("CARRIED", "XYZ", "SCALING"))
 
 
@@ -157,7 +162,8 @@ def lib():
         for name, (res, args) in (list(SIGNATURES.items()) + list(TRAIN_SIGNATURES.items())
                                    + list(MATCH_TRAIN_SIGNATURES.items()) + list(BACKBONE_TRAIN_SIGNATURES.items())
                                    + list(CLOUD_SIGNATURES.items()) + list(ICP_SIGNATURES.items())
-                                   + list(FEATURE_NN_SIGNATURES.items()) + list(ICP_PLANE_SIGNATURES.items())):
+                                   + list(FEATURE_NN_SIGNATURES.items()) + list(ICP_PLANE_SIGNATURES.items())
+                                   + list(GICP_SIGNATURES.items())):
             fn = getattr(L, name)  # AttributeError if the symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -41,7 +41,7 @@ def build(force=False, verbose=False):
                                                                  "gaussreg_hip_train_matching.h",
                                                                  "gaussreg_hip_train_backbone.h", "gaussreg_hip_cloud.h",
                                                                  "gaussreg_hip_icp.h", "gaussreg_hip_feature_nn.h",
-                                                                 "gaussreg_hip_icp_plane.h")]
+                                                                 "gaussreg_hip_icp_plane.h", "gaussreg_hip_gicp.h")]
     jobs = []
     objs = []
     for src in sources():

@@ -6,18 +6,16 @@
 //   PointToPlane::add     a matched pair in icp_sums_kernel: p = T_t src by the `apply` of the match (the same bits),
 //                         q = ref[j], v = ref_normals[j]; in fp64 r = (p - q) . v, a = [p x v, v]; n, S = sum d, the 21
 //                         distinct entries of sum a a^T and the 6 of sum a r -> 29 sums
-//   PointToPlane::update  thread 0 of icp_fold_kernel, after the stop rule has refused n < 6: solves the 6x6 system by a
-//                         cyclic Jacobi eigen-decomposition whose matrices live in LDS (run-time row and column indices,
-//                         so not in registers), refuses l_min <= 1e-12 l_max, forms dR = Rz Ry Rx and composes with
-//                         double(T_t); the fold stores T_(t+1) rounded once
+//   PointToPlane::update  thread 0 of icp_fold_kernel, after the stop rule has refused n < 6: solve6_compose of
+//                         cloud_icp_solve6.hpp, which generalised ICP shares -- the 6x6 Jacobi eigen-solve, the refusal
+//                         l_min <= 1e-12 l_max, dR = Rz Ry Rx composed with double(T_t); the fold stores T_(t+1) rounded once
 #include "../../include/gaussreg_hip_icp_plane.h"
 #include "cloud_icp_shared.hpp"
+#include "cloud_icp_solve6.hpp"
 
 namespace gr {
 namespace {
 
-constexpr int P_H = 2, P_G = 23;
-constexpr int PLANE_SWEEPS = 32;
 constexpr int FLAG_NORMALS = 2;
 
 __global__ __launch_bounds__(THREADS) void icpp_normals_kernel(const float* __restrict__ normals, int64_t count,
@@ -65,85 +63,8 @@ struct PointToPlane {
     }
   }
 
-  __device__ static bool update(const double* sum, const float* T, const Args&, float* Tn) {
-    __shared__ double Hm[36], Vm[36], ys[6], xs[6];  // thread 0's 6x6 solve: indexed at run time, so in LDS
-    // H and V = I
-    int e = P_H;
-    double fro2 = 0.0;
-    for (int c = 0; c < 6; ++c)
-      for (int d = c; d < 6; ++d) {
-        const double h = sum[e++];
-        Hm[c * 6 + d] = Hm[d * 6 + c] = h;
-        fro2 += (c == d ? 1.0 : 2.0) * h * h;
-      }
-    for (int k = 0; k < 36; ++k) Vm[k] = (k % 7 == 0) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < PLANE_SWEEPS; ++sweep) {
-      double off = 0.0;
-      for (int p = 0; p < 5; ++p)
-        for (int r = p + 1; r < 6; ++r) off += Hm[p * 6 + r] * Hm[p * 6 + r];
-      if (off <= 1e-30 * fro2) break;
-#pragma unroll 1
-      for (int p = 0; p < 5; ++p) {
-#pragma unroll 1
-        for (int r = p + 1; r < 6; ++r) {
-          const double hpr = Hm[p * 6 + r];
-          if (fabs(hpr) < 1e-300) continue;
-          const double theta = (Hm[r * 6 + r] - Hm[p * 6 + p]) / (2.0 * hpr);
-          const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-          for (int k = 0; k < 6; ++k) {
-            const double a = Hm[k * 6 + p], b = Hm[k * 6 + r];
-            Hm[k * 6 + p] = c * a - s * b;
-            Hm[k * 6 + r] = s * a + c * b;
-          }
-          for (int k = 0; k < 6; ++k) {
-            const double a = Hm[p * 6 + k], b = Hm[r * 6 + k];
-            Hm[p * 6 + k] = c * a - s * b;
-            Hm[r * 6 + k] = s * a + c * b;
-          }
-          for (int k = 0; k < 6; ++k) {
-            const double a = Vm[k * 6 + p], b = Vm[k * 6 + r];
-            Vm[k * 6 + p] = c * a - s * b;
-            Vm[k * 6 + r] = s * a + c * b;
-          }
-        }
-      }
-    }
-    double lmin = Hm[0], lmax = Hm[0];
-    for (int k = 1; k < 6; ++k) {
-      lmin = fmin(lmin, Hm[k * 7]);
-      lmax = fmax(lmax, Hm[k * 7]);
-    }
-    if (!(lmin > 1e-12 * lmax)) return false;  // a NaN as well
-    for (int k = 0; k < 6; ++k) {  // y = diag(1 / l) V^T g
-      double a = 0.0;
-      for (int j = 0; j < 6; ++j) a += Vm[j * 6 + k] * sum[P_G + j];
-      ys[k] = a / Hm[k * 7];
-    }
-    for (int i = 0; i < 6; ++i) {  // x = -V y
-      double a = 0.0;
-      for (int k = 0; k < 6; ++k) a += Vm[i * 6 + k] * ys[k];
-      xs[i] = -a;
-    }
-    const double ca = cos(xs[0]), sa = sin(xs[0]), cb = cos(xs[1]), sb = sin(xs[1]), cg = cos(xs[2]), sg = sin(xs[2]);
-    // dR = Rz(gamma) Ry(beta) Rx(alpha)
-    const double dR[9] = {cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa,
-                          sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa,
-                          -sb,     cb * sa,                cb * ca};
-    const double dt[3] = {xs[3], xs[4], xs[5]};
-    double A[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) A[k] = (double)T[k];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        double a = (dR[r * 3] * A[c] + dR[r * 3 + 1] * A[4 + c]) + dR[r * 3 + 2] * A[8 + c];
-        if (c == 3) a += dt[r];
-        Tn[r * 4 + c] = (float)a;
-      }
-    }
-    return true;
+  __device__ static __forceinline__ bool update(const double* sum, const float* T, const Args&, float* Tn) {
+    return solve6_compose(sum, T, Tn);
   }
 };
 

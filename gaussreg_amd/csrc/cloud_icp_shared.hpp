@@ -1,8 +1,8 @@
-// The ICP loop (DESIGN.md 3.11 point-to-point, 3.14 point-to-plane): the fp32 transform, the kernels that order the source
-// once and match it every round, the block sum, the fold kernel with the history row, the stop rule and the epilogue, the
-// scatter of the reported matches, the workspace and the host driver.  cloud_icp.hip and cloud_icp_plane.hip each add an
-// estimator -- its sums, what a matched pair adds to them and its update -- and instantiate the loop with it.  Everything is in the
-// anonymous namespace, so each of the two files compiles its own copy of the kernels.
+// The ICP loop (DESIGN.md 3.11 point-to-point, 3.14 point-to-plane, 3.15 generalised): the fp32 transform, the kernels that
+// order the source once and match it every round, the block sum, the fold kernel with the history row, the stop rule and the
+// epilogue, the scatter of the reported matches, the workspace and the host driver.  cloud_icp.hip, cloud_icp_plane.hip and
+// cloud_icp_gicp.hip each add an estimator -- its sums, what a matched pair adds to them and its update -- and instantiate the
+// loop with it.  Everything is in the anonymous namespace, so each of the three files compiles its own copy of the kernels.
 //
 // An estimator E provides
 //   NSUM, I_N, I_S     the number of fp64 sums of a partial row and where n and S = sum d sit among them

@@ -19,6 +19,11 @@ with TransformationEstimationPointToPoint(with_scaling); parity with Open3D is u
 
 is the same loop with the point-to-plane update (csrc/cloud_icp_plane.hip): rigid only, the estimator for
 scans of walls, floors and table tops, along which point-to-point slides slowly.
+
+    res = icp_generalized(src, ref, src_cov, ref_cov, init_transform=T0, max_dist=0.1)
+
+is the same loop with the update of generalised ICP (csrc/cloud_icp_gicp.hip): every residual weighted by
+(C_ref + R C_src R^T)^-1, with the (N, 6) covariances of `gaussreg_amd.covariances` -- a scene's own Gaussians among them.
 """
 import ctypes
 import sys
@@ -67,7 +72,7 @@ def _transform0(init_transform):
 
 
 def _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness, relative_rmse):
-    """The checks both estimators share -> (float32(max_dist^2), relative_fitness, relative_rmse) as floats."""
+    """The checks the estimators share -> (float32(max_dist^2), relative_fitness, relative_rmse) as floats."""
     _check_cloud(src_points, "src_points")
     _check_cloud(ref_points, "ref_points")
     if ref_points.shape[0] < 1:
@@ -88,9 +93,9 @@ def _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_
 
 
 def _run(entry, src_points, ref_points, extra_clouds, init_transform, extra_scalars, cap, max_iterations, relative_fitness,
-         relative_rmse, return_correspondences, return_history):
-    """Allocate the outputs, call `entry` -- gr_cloud_icp(src, n, ref, *extra_clouds, m, T0, cap, *extra_scalars, ...) --
-    and read the result."""
+         relative_rmse, return_correspondences, return_history, src_extra=()):
+    """Allocate the outputs, call `entry` -- gr_cloud_icp(src, n, *src_extra, ref, *extra_clouds, m, T0, cap, *extra_scalars,
+    ...) -- and read the result."""
     t0 = _transform0(init_transform)
     src, ref = src_points.detach(), ref_points.detach()
     dev, n, m = src.device, src.shape[0], ref.shape[0]
@@ -100,7 +105,7 @@ def _run(entry, src_points, ref_points, extra_clouds, init_transform, extra_scal
     dist2 = torch.empty(n, dtype=torch.float32, device=dev) if return_correspondences else None
     history = torch.zeros((max_iterations + 1, 16), dtype=torch.float64, device=dev) if return_history else None
     h_status = (ctypes.c_int * 2)(0, 0)
-    _finite(lambda: _lib.call(dev, entry, src, n, ref, *extra_clouds, m, t0.ctypes.data_as(ctypes.c_void_p), cap, *extra_scalars,
+    _finite(lambda: _lib.call(dev, entry, src, n, *src_extra, ref, *extra_clouds, m, t0.ctypes.data_as(ctypes.c_void_p), cap, *extra_scalars,
                               max_iterations, relative_fitness, relative_rmse, transform, stats, index, dist2, history, h_status,
                               ws=getattr(_lib.lib(), entry + "_workspace_bytes")(n, m, max_iterations)))
     status, iterations = STATUS[h_status[0]], int(h_status[1])
@@ -148,6 +153,47 @@ def icp_point_to_plane(src_points, ref_points, ref_normals, init_transform=None,
     except RuntimeError as e:
         if "normals must be finite" in str(e):
             raise ValueError("normals must be finite") from None
+        raise
+
+
+def _check_covariances(cov, name, points, points_name):
+    if not isinstance(cov, torch.Tensor) or cov.dim() != 2 or cov.shape[1] != 6:
+        raise ValueError(f"{name}: must be a tensor of shape (N, 6), got shape {tuple(getattr(cov, 'shape', ()))}")
+    if cov.dtype != torch.float32:
+        raise ValueError(f"{name}: dtype {cov.dtype}, must be float32")
+    if not cov.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    if not cov.is_cuda:
+        raise ValueError(f"{name}: on {cov.device}, must be on the GPU (there is no CPU fallback)")
+    if cov.shape[0] != points.shape[0]:
+        raise ValueError(f"{name}: {cov.shape[0]} rows for {points.shape[0]} points of {points_name}")
+    if cov.device != points.device:
+        raise ValueError(f"{points_name} is on {points.device}, {name} on {cov.device}")
+
+
+@torch.no_grad()
+def icp_generalized(src_points, ref_points, src_covariances, ref_covariances, init_transform=None, max_dist=0.1,
+                    max_iterations=30, relative_fitness=1e-6, relative_rmse=1e-6, return_correspondences=False,
+                    return_history=False):
+    """Generalised ICP (csrc/cloud_icp_gicp.hip, DESIGN.md 3.15, include/gaussreg_hip_gicp.h): the loop of `icp` -- the same
+    evaluation, stop rule, statuses and history, fitness and inlier RMSE Euclidean -- whose update minimises
+    sum d^T (C_ref + A C_src A^T)^-1 d over the matched pairs, d = T p - q, A the rotation of the current transform, linearised
+    there and solved in float64 on the device; rigid only.  `src_covariances` (N, 6) and `ref_covariances` (M, 6) fp32, the
+    upper triangles xx, xy, xz, yy, yz, zz (`covariances.covariances_from_gaussians`, `covariances_from_normals`,
+    `estimate_covariances`), finite; a pair whose combined covariance is singular (two zero rows) drops out of the update
+    and still counts.  Fewer than three matches or a system without a unique solution is "degenerate".  Open3D's
+    TransformationEstimationForGeneralizedICP; parity unpinned."""
+    cap, relative_fitness, relative_rmse = _check_arguments(src_points, ref_points, max_dist, max_iterations, relative_fitness,
+                                                            relative_rmse)
+    _check_covariances(src_covariances, "src_covariances", src_points, "src_points")
+    _check_covariances(ref_covariances, "ref_covariances", ref_points, "ref_points")
+    try:
+        return _run("gr_cloud_gicp", src_points, ref_points, (ref_covariances.detach(),), init_transform, (), cap,
+                    max_iterations, relative_fitness, relative_rmse, return_correspondences, return_history,
+                    src_extra=(src_covariances.detach(),))
+    except RuntimeError as e:
+        if "covariances must be finite" in str(e):
+            raise ValueError("covariances must be finite") from None
         raise
 
 
